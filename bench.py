@@ -12,10 +12,10 @@ Modes
   default        K independent batches per rank (4 distinct key sets, rotated), `--pipeline` of them in flight on as
                  many HIP streams; with N > 1 every rank owns its own batch stream (weak scaling: the 14 400-state N2
                  space cannot supply N x 10 000 unique samples for one table) and the per-step accumulators [K, 4]
-                 are summed over the ranks by one RCCL all-reduce at the end of the timed region.  The same process
-                 also measures, and reports inside the same JSON line,
-                   * `serial` (before the warm-up): the step one batch at a time, 2 000 steps (kernel durations with
-                     the GPU to themselves; also what brings a freshly started GPU to its sustained state);
+                 are summed over the ranks by one RCCL all-reduce at the end of the timed region.  Before the warm-up
+                 the step runs 2 000 times one batch at a time: what brings a freshly started GPU to its sustained
+                 state.  With `--full` the same process also measures, and reports inside the same JSON line,
+                   * `serial`: those 2 000 steps timed (kernel durations with the GPU to themselves);
                    * `config4_row_sharded`: BASELINE config 4 / north_star's split — ONE Li2O table of 50 000 keys,
                      rows sharded over the ranks (below) — so that a 1/2/4/8-GPU sweep of the default command also
                      yields the strong-scaling curve of the sharded table.
@@ -24,9 +24,13 @@ Modes
                  `naqs_eloc` for its rows against the whole table, ONE all-reduce per step sums the 4 energy
                  accumulators.  Total work is fixed -> "scaling": "strong".
 
-Prints ONE JSON line on rank 0 (contract in the task statement) incl. `roofline` and `cpu_baseline`; everything
-in it is measured by this run except the fields tagged `"replayed": true` (hardware counters, which only a
-rocprofv3 --pmc pass can produce: they are read from the committed profiles/ file named beside them).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the `--steps` steps and reports the headline
+(`metric`, `value`, `unit`, `ms_per_step`, `dtype`, ...), nothing else.  `--full` adds what takes work of its own: the
+kernel-duration brackets of the timed region and the `roofline` built on them, `serial`, `config4_row_sharded`,
+`train_step` and `cpu_baseline`; everything in it is measured by this run except the fields tagged `"replayed": true`
+(hardware counters, which only a rocprofv3 --pmc pass can produce: they are read from the committed profiles/ file
+named beside them).  `--dump-outputs DIR` writes what the timed path returned in its last step (log psi, E_loc, the
+weighted sums) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import ctypes
@@ -362,13 +366,16 @@ def dry_run(args, world, rank):
 # ------------------------------------------------------------------------------------------------------------------
 # the row-sharded table (config 4 / north_star's split)
 # ------------------------------------------------------------------------------------------------------------------
-def run_row_sharded(dev, world, rank, use_dist, molecule, M, steps, warmup, depth=2, streams=None, emulate=False):
+def run_row_sharded(dev, world, rank, use_dist, molecule, M, steps, warmup, depth=2, streams=None, emulate=False, prof=True,
+                    want_outputs=False):
     """-> dict with ms_per_step, samples/s and the kernel durations of one sharded table of M keys.  `depth` evaluations
     of the table are in flight (one HIP stream and one handle pair each, as in the default mode): the E_loc kernel and the
     collectives of one overlap the log-psi kernel of the next.
     emulate (--emulate-world, single process): this process plays rank `rank` of `world` WITHOUT the others — it evaluates
     log psi for its own padded row shard and E_loc for its own rows against the WHOLE table, which is evaluated once up
-    front outside the timed region and stands in for what the all-gather would deliver; no collective is issued."""
+    front outside the timed region and stands in for what the all-gather would deliver; no collective is issued.
+    prof=False: no kernel-duration brackets in the timed region (the kernel fields read 0).  want_outputs: the dict also
+    holds `_outputs`, what the last timed step returned on this rank (the table's log psi, E_loc of its rows, the sums)."""
     import torch
     import torch.distributed as dist
     from naqs_amd import hamiltonian, packing
@@ -445,9 +452,10 @@ def run_row_sharded(dev, world, rank, use_dist, molecule, M, steps, warmup, dept
         step(i)
     fence()
     stride = max(1, min(PROF_STRIDE, (steps // depth) // 4))
-    for h_, n_ in zip(hams, nets):
-        h_.prof_enable(steps // stride + 1, stride)
-        n_.prof_enable(steps // stride + 1, stride)
+    if prof:
+        for h_, n_ in zip(hams, nets):
+            h_.prof_enable(steps // stride + 1, stride)
+            n_.prof_enable(steps // stride + 1, stride)
     t0 = time.perf_counter()
     for i in range(steps):
         step(warmup + i)
@@ -456,9 +464,10 @@ def run_row_sharded(dev, world, rank, use_dist, molecule, M, steps, warmup, dept
     if use_dist:
         dist.barrier()
     e_ms = e_n = p_ms = p_n = 0
-    for h_, n_ in zip(hams, nets):
-        a_, b_ = h_.prof_read(); e_ms += a_; e_n += b_; h_.prof_enable(0)
-        a_, b_ = n_.prof_read(); p_ms += a_; p_n += b_; n_.prof_enable(0)
+    if prof:
+        for h_, n_ in zip(hams, nets):
+            a_, b_ = h_.prof_read(); e_ms += a_; e_n += b_; h_.prof_enable(0)
+            a_, b_ = n_.prof_read(); p_ms += a_; p_n += b_; n_.prof_enable(0)
     t = torch.tensor([dt], dtype=torch.float64, device=dev)
     if use_dist and world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -478,9 +487,13 @@ def run_row_sharded(dev, world, rank, use_dist, molecule, M, steps, warmup, dept
            "eloc_kernel_name": hams[0].last_kernel(), "logpsi_kernel_name": nets[0].last_kernel()}
     b_alg = algorithmic_bytes(e - b, ham.K, ham.Kxy) if e > b else 0
     res["eloc_algorithmic_GBps"] = b_alg / t_eloc / 1e9 if t_eloc > 0 else 0.0
-    issue = issue_roofline(f"{molecule}_{M}", t_eloc) if world == 1 else None
+    issue = issue_roofline(f"{molecule}_{M}", t_eloc) if world == 1 and prof else None
     if issue:
         res["eloc_issue"] = issue
+    if want_outputs:
+        d = (warmup + steps - 1) % depth
+        lp_table = table[d] if use_dist else (lp_mine[d] if full_table is None else full_table)
+        res["_outputs"] = {"log_psi": lp_table[:M].cpu().numpy(), "e_loc": eloc[d].cpu().numpy(), "sums": s}
     for h_ in hams:
         h_.close()
     for n_ in nets:
@@ -595,6 +608,37 @@ def dtype_label(kernel_name=None):
     fmt = phase_format(kernel_name)
     net = {2: "f16x2-split MFMA, f32-equivalent", 1: "bf16x3-split MFMA, f32-equivalent", 0: "f32 MFMA"}[fmt if fmt in (0, 1, 2) else 2]
     return f"f32 network ({net}) / f64 E_loc"
+
+
+def headline_roofline(args, ham, M, lp_name, t_kernel, t_mlp, serial):
+    """--full: `roofline` of the default mode from the kernel brackets of the timed region (t_kernel: E_loc, t_mlp: log psi)
+    and, where it ran, the serial segment's."""
+    amp_in_kernel = "amplitude" in lp_name                            # the kernel's own name says whether the items ran inside it
+    eloc_roof = eloc_roofline(ham.last_kernel(), t_kernel, M, ham.K, ham.Kxy, f"{args.molecule}_{M}",
+                              serial["eloc_kernel_us"] * 1e-6 if serial and serial["eloc_kernel_us"] > 0 else None)
+    mlp_roof = logpsi_roofline(lp_name, t_mlp, ham.n_qubits, M, amp_in_kernel,
+                               serial["logpsi_kernel_us"] * 1e-6 if serial and serial["logpsi_kernel_us"] > 0 else None)
+    # HBM bytes per launch: hardware counters, from the committed rocprofv3 --pmc passes of this same command
+    # (tools/collect_pmc.py; FETCH_SIZE/WRITE_SIZE in separate passes, gfx950 corrections applied there) — replayed only
+    # when the file was collected on the library build that is running (source hash)
+    pmc = _load_json(PMC_TRAFFIC)
+    if counters_match_library(pmc) and args.molecule == "N2" and M == 10000:   # the PMC passes were taken on this workload
+        for roof, name in ((eloc_roof, "eloc_kernel"), (mlp_roof, "phase_kernel")):
+            if name in pmc:
+                roof["traffic"] = pmc[name]["hbm_bytes_per_launch"]
+                roof["traffic_source"] = {"replayed": True, "file": PMC_TRAFFIC, "source_hash": pmc["_source_hash"]}
+    dominant, other = (mlp_roof, eloc_roof) if t_mlp >= t_kernel else (eloc_roof, mlp_roof)
+    roofline = dict(dominant)
+    roofline["other_kernels"] = [other]
+    return roofline
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs DIR: what the timed path returned in its last step, as DIR/<name>.npy (float32 / float64 as returned)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -714,6 +758,8 @@ def worker(args):
     # 51.2 and 61.0 — the figures `--steps 400` gives regardless (measured in one gpurun call).
     # (an event pair costs ~4 us of queue time on its stream: at most every 10th launch of a handle is bracketed, and a
     # short region — the driver's `--steps 20` is 10 launches per handle — gets two brackets per handle, not one per step)
+    # A plain run keeps the segment as the load that brings the chip to its sustained state, without brackets or report;
+    # --full times it and brackets its kernels (`serial`, `roofline.isolated`).
     stride = max(1, min(PROF_STRIDE, (args.steps // depth) // 2))
     import gc
     gc.collect()
@@ -722,17 +768,19 @@ def worker(args):
         for _ in range(min(args.warmup, 10)):
             step(0)
         fence()
-        hams[0].prof_enable(n_serial // PROF_STRIDE + 1, PROF_STRIDE)
-        nets[0].prof_enable(n_serial // PROF_STRIDE + 1, PROF_STRIDE)
+        if args.full:
+            hams[0].prof_enable(n_serial // PROF_STRIDE + 1, PROF_STRIDE)
+            nets[0].prof_enable(n_serial // PROF_STRIDE + 1, PROF_STRIDE)
         t1 = time.perf_counter()
         for _ in range(n_serial):
             step(0)
         fence()
         dts = time.perf_counter() - t1
-        e_ms, e_n = hams[0].prof_read(); hams[0].prof_enable(0)
-        p_ms, p_n = nets[0].prof_read(); nets[0].prof_enable(0)
-        serial = {"ms_per_step": dts / n_serial * 1e3, "steps": n_serial, "eloc_kernel_us": e_ms / max(e_n, 1) * 1e3,
-                  "logpsi_kernel_us": p_ms / max(p_n, 1) * 1e3, "measured": "this run, before the timed region"}
+        if args.full:
+            e_ms, e_n = hams[0].prof_read(); hams[0].prof_enable(0)
+            p_ms, p_n = nets[0].prof_read(); nets[0].prof_enable(0)
+            serial = {"ms_per_step": dts / n_serial * 1e3, "steps": n_serial, "eloc_kernel_us": e_ms / max(e_n, 1) * 1e3,
+                      "logpsi_kernel_us": p_ms / max(p_n, 1) * 1e3, "measured": "this run, before the timed region"}
 
     # As little host work as possible between the serial segment, the warm-up and the timed region: an idle GPU drops its clocks
     # within a millisecond or so and takes milliseconds of load to come back.  The collector ran before the serial segment and is
@@ -748,7 +796,8 @@ def worker(args):
         step()
     fence(first_row=first_warm)                  # (also sets the communicator up outside the timed region)
     t_prep = time.perf_counter()
-    if os.environ.get("NAQS_BENCH_NOPROF") != "1":      # (diagnostic: the timed region without the hipEvent brackets)
+    prof = args.full and os.environ.get("NAQS_BENCH_NOPROF") != "1"     # (diagnostic: --full without the hipEvent brackets)
+    if prof:
         for h_, n_ in zip(hams, nets):
             h_.prof_enable(args.steps // stride + 1, stride)
             n_.prof_enable(args.steps // stride + 1, stride)
@@ -771,16 +820,21 @@ def worker(args):
         dist.barrier()
     last_row = n_done[0] - 1
     kern_ms = launches = mlp_ms = mlp_launches = 0
-    for h_, n_ in zip(hams, nets):
-        a, b = h_.prof_read(); kern_ms += a; launches += b
-        h_.prof_enable(0)
-        a, b = n_.prof_read(); mlp_ms += a; mlp_launches += b
-        n_.prof_enable(0)
+    if prof:
+        for h_, n_ in zip(hams, nets):
+            a, b = h_.prof_read(); kern_ms += a; launches += b
+            h_.prof_enable(0)
+            a, b = n_.prof_read(); mlp_ms += a; mlp_launches += b
+            n_.prof_enable(0)
     t = torch.tensor([dt], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
     s = acc_all[last_row].cpu().numpy()
+    # what the last timed step's naqs_logpsi_eloc call returned: its pipeline slot's log psi and E_loc, its row of sums
+    d_last = last_row % depth
+    outputs = {"log_psi": log_psis[d_last].cpu().numpy(), "e_loc": elocs[d_last].cpu().numpy(), "sums": s} \
+        if args.dump_outputs and rank == 0 else None
     for h_ in hams[1:]:
         h_.close()
     for n_ in nets[1:]:
@@ -788,7 +842,7 @@ def worker(args):
 
     # BASELINE config 4 in the same run (every rank takes part: it has collectives)
     config4 = None
-    if not args.no_config4 and args.molecule == "N2":
+    if args.full and not args.no_config4 and args.molecule == "N2":
         try:
             config4, _ = run_row_sharded(dev, world, rank, use_dist, "Li2O", 50000, steps=max(50, min(args.steps, 100)),
                                          warmup=max(2, min(args.warmup, 10)), depth=depth, streams=streams)
@@ -797,26 +851,7 @@ def worker(args):
 
     out = None
     if rank == 0:
-        t_kernel = kern_ms / max(launches, 1) * 1e-3
-        t_mlp = mlp_ms / max(mlp_launches, 1) * 1e-3
         lp_name = nets[0].last_kernel()
-        amp_in_kernel = "amplitude" in lp_name                            # the kernel's own name says whether the items ran inside it
-        eloc_roof = eloc_roofline(ham.last_kernel(), t_kernel, M, ham.K, ham.Kxy, f"{args.molecule}_{M}",
-                                  serial["eloc_kernel_us"] * 1e-6 if serial and serial["eloc_kernel_us"] > 0 else None)
-        mlp_roof = logpsi_roofline(lp_name, t_mlp, ham.n_qubits, M, amp_in_kernel,
-                                   serial["logpsi_kernel_us"] * 1e-6 if serial and serial["logpsi_kernel_us"] > 0 else None)
-        # HBM bytes per launch: hardware counters, from the committed rocprofv3 --pmc passes of this same command
-        # (tools/collect_pmc.py; FETCH_SIZE/WRITE_SIZE in separate passes, gfx950 corrections applied there) — replayed only
-        # when the file was collected on the library build that is running (source hash)
-        pmc = _load_json(PMC_TRAFFIC)
-        if counters_match_library(pmc) and args.molecule == "N2" and M == 10000:   # the PMC passes were taken on this workload
-            for roof, name in ((eloc_roof, "eloc_kernel"), (mlp_roof, "phase_kernel")):
-                if name in pmc:
-                    roof["traffic"] = pmc[name]["hbm_bytes_per_launch"]
-                    roof["traffic_source"] = {"replayed": True, "file": PMC_TRAFFIC, "source_hash": pmc["_source_hash"]}
-        dominant, other = (mlp_roof, eloc_roof) if t_mlp >= t_kernel else (eloc_roof, mlp_roof)
-        roofline = dict(dominant)
-        roofline["other_kernels"] = [other]
         out = {
             "metric": f"unique samples/sec through E_loc + log-psi eval ({args.molecule}, {ham.n_qubits} qubits)",
             "value": world * M * args.steps / dt,
@@ -839,13 +874,15 @@ def worker(args):
                                  if use_dist else "single process, no process group"),
                        "ranks_detail": rank_info,
                        "energy": float(s[0] / s[3])},
-            "roofline": roofline,
         }
+        if args.full:
+            out["roofline"] = headline_roofline(args, ham, M, lp_name, kern_ms / max(launches, 1) * 1e-3,
+                                                mlp_ms / max(mlp_launches, 1) * 1e-3, serial)
         if serial is not None:
             out["serial"] = serial
         if config4 is not None:
             out["config4_row_sharded"] = config4
-        if not args.no_train_step and world == 1:
+        if args.full and not args.no_train_step and world == 1:
             # the real workload's step, so that the driver's line carries it (three molecules, ~1 s each)
             ts = {"what": "one VMC training step (sampler + forward + E_loc + backward + Adam + re-pack) of the published ansatz "
                           "through PartialSamplingOptimizer.run, after 40 steps from a random initialisation"}
@@ -855,8 +892,10 @@ def worker(args):
                 except Exception as ex:                                       # the headline must survive a secondary failure
                     ts[mol_] = {"error": f"{type(ex).__name__}: {ex}"}
             out["train_step"] = ts
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(ham_p, keys_np, log_psi_np, wf_args)
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
     finish(out)
     return 0
 
@@ -865,21 +904,13 @@ def sharded_main(args, dev, world, rank, use_dist, rank_info=None):
     """--shard rows: the sharded table is the measurement (BASELINE config 4 with --molecule Li2O --samples 50000)."""
     import torch.distributed as dist
     res, (ham_p, keys_np, log_psi_np, wf_args) = run_row_sharded(dev, world, rank, use_dist, args.molecule, args.samples,
-                                                                 args.steps, args.warmup, depth=max(1, args.pipeline))
+                                                                 args.steps, args.warmup, depth=max(1, args.pipeline),
+                                                                 prof=args.full, want_outputs=bool(args.dump_outputs))
+    outputs = res.pop("_outputs", None)
     out = None
     if rank == 0:
-        t_eloc, t_lp = res["eloc_kernel_us"] * 1e-6, res["logpsi_kernel_us"] * 1e-6
         rows, S = res["rows_per_rank"], res["logpsi_rows_per_rank"]
-        from naqs_amd import packing  # noqa: F401
-        K, Kxy = ham_p.K, len(np.unique(ham_p.xy))
-        eloc_roof = eloc_roofline(res.pop("eloc_kernel_name", "eloc_kernel2"), t_eloc, rows, K, Kxy,
-                                  f"{args.molecule}_{args.samples}" if world == 1 else None, None)
-        res.pop("eloc_issue", None)
         lp_name = res.pop("logpsi_kernel_name", "phase_kernel_h")
-        mlp_roof = logpsi_roofline(lp_name, t_lp, ham_p.n_qubits, S, "amplitude" in lp_name, None)
-        dominant, other = (mlp_roof, eloc_roof) if t_lp >= t_eloc else (eloc_roof, mlp_roof)
-        roofline = dict(dominant)
-        roofline["other_kernels"] = [other]
         out = {"metric": f"unique samples/sec through E_loc + log-psi eval ({args.molecule}, {ham_p.n_qubits} qubits), one "
                          f"row-sharded table",
                "value": res["value"], "unit": "unique samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -888,10 +919,20 @@ def sharded_main(args, dev, world, rank, use_dist, rank_info=None):
                "config": {"workload": res["workload"], "collectives_per_step": res["collectives_per_step"],
                           "ranks": (f"{dist.get_world_size()} {'RCCL' if dist.get_backend() == 'nccl' else dist.get_backend()} rank(s)"
                                     if use_dist else "single process, no process group"),
-                          "ranks_detail": rank_info, "rows_per_rank": rows, "energy": res["energy"]},
-               "roofline": roofline}
-        if not args.no_cpu_baseline and world == 1:
+                          "ranks_detail": rank_info, "rows_per_rank": rows, "energy": res["energy"]}}
+        if args.full:
+            t_eloc, t_lp = res["eloc_kernel_us"] * 1e-6, res["logpsi_kernel_us"] * 1e-6
+            K, Kxy = ham_p.K, len(np.unique(ham_p.xy))
+            eloc_roof = eloc_roofline(res.pop("eloc_kernel_name", "eloc_kernel2"), t_eloc, rows, K, Kxy,
+                                      f"{args.molecule}_{args.samples}" if world == 1 else None, None)
+            mlp_roof = logpsi_roofline(lp_name, t_lp, ham_p.n_qubits, S, "amplitude" in lp_name, None)
+            dominant, other = (mlp_roof, eloc_roof) if t_lp >= t_eloc else (eloc_roof, mlp_roof)
+            out["roofline"] = dict(dominant)
+            out["roofline"]["other_kernels"] = [other]
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(ham_p, keys_np, log_psi_np, wf_args)
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
     finish(out)
     return 0
 
@@ -1044,6 +1085,13 @@ def parse(argv=None):
     ap.add_argument("--shard", choices=["batches", "rows"], default="batches",
                     help="batches: independent batches per rank (weak scaling, default); rows: ONE table, rows sharded over "
                          "the ranks, all-gather of log psi + all-reduce of the accumulators per step (strong scaling)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: kernel-duration brackets in the timed region and "
+                         "`roofline`, `serial`, `config4_row_sharded`, `train_step`, `cpu_baseline` (the --no-* options "
+                         "below leave parts of it out)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one returned (log psi, E_loc, weighted sums) as "
+                         "DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-serial-segment", action="store_true",
                     help="skip the one-batch-at-a-time segment that precedes the timed region (`serial`, `roofline.isolated`)")
@@ -1057,7 +1105,10 @@ def parse(argv=None):
                          "--emulate-world 1,2,4,8 --molecule Li2O --samples 50000; prints the implied strong-scaling ceiling")
     ap.add_argument("--pipeline", type=int, default=2,
                     help="independent batches in flight (HIP streams, one Hamiltonian/network handle pair each); 1 = serial")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.dump_outputs and args.emulate_world:
+        ap.error("--dump-outputs: --emulate-world is a scaling model, it has no outputs of its own")
+    return args
 
 
 def main(argv=None):

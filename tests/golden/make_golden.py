@@ -153,6 +153,29 @@ def gen_packing_hashes():
         print(f"[packing] {mol}: N={N} K={len(c)} {h[:16]}")
     with open(os.path.join(OUT, "packing_sha256.json"), "w") as f:
         json.dump(out, f, indent=1, sort_keys=True)
+    gen_packing_terms(sorted(out))
+
+
+def gen_packing_terms(mols):
+    """The Pauli terms of the same qubit-Hamiltonian pickles as arrays -> packing_terms.npz, so that tests/test_packing.py
+    can pack every molecule without the folders: per molecule `<mol>:ops` (uint8 [K, n_qubits], 0/1/2/3 = I/X/Y/Z, one row
+    per term in the pickle's term order), `<mol>:coeff` (complex128 [K]) and `<mol>:electrons` ([n_electrons, multiplicity]
+    from the HDF5 file).  Each molecule's terms are rebuilt from the arrays and checked against the pickle, order included."""
+    arrays = {}
+    for mol in mols:
+        qh = rh.load_qubit_hamiltonian(mol)
+        N = rh.n_qubits_of(qh)
+        ops = np.zeros((len(qh.terms), N), np.uint8)
+        for i, term in enumerate(qh.terms):
+            for q, op in term:
+                ops[i, q] = "IXYZ".index(op)
+        coeff = np.array([complex(c) for c in qh.terms.values()], np.complex128)
+        rebuilt = [(tuple((q, "IXYZ"[o]) for q, o in enumerate(row) if o), c) for row, c in zip(ops.tolist(), coeff)]
+        assert rebuilt == [(tuple(k), complex(c)) for k, c in qh.terms.items()], mol
+        v = molecule_scalars(mol)
+        arrays[f"{mol}:ops"], arrays[f"{mol}:coeff"] = ops, coeff
+        arrays[f"{mol}:electrons"] = np.array([v["n_electrons"], v["multiplicity"]], np.int64)
+    np.savez_compressed(os.path.join(OUT, "packing_terms.npz"), **arrays)
 
 
 def gen_li2o_subset():

@@ -11,6 +11,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REQUIRED = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
             "vs_baseline", "dtype", "data", "config", "roofline"}
+HEADLINE = REQUIRED - {"roofline"}                                    # a plain run (no --full)
+FULL_ONLY = {"roofline", "serial", "config4_row_sharded", "train_step", "cpu_baseline"}
 
 
 def _bench():
@@ -58,6 +60,16 @@ def test_li2o_batch_and_row_shards():
             assert sh[0][1] == 0 and sh[-1][2] == M and all(sh[i][2] == sh[i + 1][1] for i in range(world - 1))
 
 
+def test_full_and_dump_outputs_options():
+    bench = _bench()
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+    with pytest.raises(SystemExit):
+        bench.parse(["--emulate-world", "1,2", "--dump-outputs", "out"])
+
+
 def _run_bench(argv, env_extra, timeout=300):
     env = dict(os.environ, **env_extra)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
@@ -98,17 +110,22 @@ def test_a_failing_rank_fails_the_launch():
 
 
 @pytest.mark.gpu
-def test_row_sharded_table_through_rccl_on_one_gpu():
+def test_row_sharded_table_through_rccl_on_one_gpu(tmp_path):
     """BASELINE config 4 as one rank: Li2O, ONE table of 50 000 keys, the sharded step with its collectives issued
-    through an RCCL group of size 1 (all-gather of the log-psi table, all-reduce of the accumulators)."""
+    through an RCCL group of size 1 (all-gather of the log-psi table, all-reduce of the accumulators); the outputs of
+    the last step are the whole table's."""
     r, lines = _run_bench(["--gpus", "1", "--shard", "rows", "--molecule", "Li2O", "--samples", "50000", "--steps", "20",
-                           "--warmup", "3", "--no-cpu-baseline"], {"NAQS_BENCH_FORCE_DIST": "1"}, timeout=900)
+                           "--warmup", "3", "--no-cpu-baseline", "--full", "--dump-outputs", str(tmp_path)],
+                          {"NAQS_BENCH_FORCE_DIST": "1"}, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads(lines[-1])
     assert REQUIRED <= set(d) and d["scaling"] == "strong" and d["n_gpus"] == 1 and d["value"] > 1e6
     assert "1 RCCL rank(s)" in d["config"]["ranks"] and d["config"]["rows_per_rank"] == 50000
     assert d["config"]["ranks_detail"] == [{"rank": 0, "device": 0, "communicator_world_size": 1}]     # what the communicator saw
     assert np.isfinite(d["config"]["energy"]) and "all-gather" in d["config"]["collectives_per_step"]
+    lp, e, s = (np.load(tmp_path / f"{n}.npy") for n in ("log_psi", "e_loc", "sums"))
+    assert lp.shape == (50000, 2) and lp.dtype == np.float32 and e.shape == (50000, 2) and e.dtype == np.float64
+    assert s.shape == (4,) and s[0] / s[3] == d["config"]["energy"] and np.isfinite(lp).all() and np.isfinite(e).all()
 
 
 @pytest.mark.gpu
@@ -131,7 +148,7 @@ def test_two_ranks_on_one_gpu_shard_one_table_to_the_same_energy():
 def test_two_ranks_on_one_gpu_weak_mode_runs():
     """The default (independent batches per rank) mode with two ranks: one all-reduce of the accumulators at the end of
     the timed region, then the row-sharded config-4 table across both ranks, one JSON line from rank 0."""
-    r, lines = _run_bench(["--gpus", "2", "--steps", "20", "--warmup", "4", "--no-cpu-baseline"],
+    r, lines = _run_bench(["--gpus", "2", "--steps", "20", "--warmup", "4", "--no-cpu-baseline", "--full"],
                           {"NAQS_BENCH_ONE_DEVICE": "1", "NAQS_BENCH_BACKEND": "gloo"}, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads(lines[-1])
@@ -145,7 +162,7 @@ def test_two_ranks_on_one_gpu_weak_mode_runs():
 def test_default_line_is_measured_in_this_run():
     """serial figures and the config-4 table are measured by the same process, nothing is replayed from a file except
     the hardware-counter fields, which say so."""
-    r, lines = _run_bench(["--gpus", "1", "--steps", "40", "--warmup", "5", "--no-cpu-baseline"], {}, timeout=900)
+    r, lines = _run_bench(["--gpus", "1", "--steps", "40", "--warmup", "5", "--no-cpu-baseline", "--full"], {}, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads(lines[-1])
     assert d["serial"]["measured"].startswith("this run") and "source" not in d["serial"]
@@ -163,7 +180,8 @@ def test_default_line_is_measured_in_this_run():
 @pytest.mark.gpu
 @pytest.mark.parametrize("extra", [["--no-config4"], ["--pipeline", "1", "--no-config4"]])
 def test_bench_prints_one_json_line_last(extra):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "5", "--no-cpu-baseline"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "5", "--no-cpu-baseline",
+           "--full"] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -171,3 +189,26 @@ def test_bench_prints_one_json_line_last(extra):
     assert REQUIRED <= set(d) and d["n_gpus"] == 1 and d["steps"] == 30 and d["value"] > 1e6
     assert {"bound", "achieved", "peak", "unit", "frac", "traffic"} <= set(d["roofline"])
     assert sum(1 for l in lines if l.lstrip().startswith("{")) == 1
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """The plain command measures the headline and nothing else; `--steps` is the number of timed steps behind
+    `ms_per_step`; `--dump-outputs` writes the last timed step's log psi, E_loc and weighted sums, and two runs with the
+    same arguments work on the same inputs."""
+    runs = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        r, lines = _run_bench(["--gpus", "1", "--steps", "30", "--warmup", "5", "--dump-outputs", str(out)], {}, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads(lines[-1])
+        assert HEADLINE <= set(d) and not (FULL_ONLY & set(d)) and d["n_gpus"] == 1 and d["steps"] == 30
+        assert d["value"] > 1e6 and d["value"] == pytest.approx(10000 / (d["ms_per_step"] * 1e-3), rel=1e-9)
+        assert sum(1 for l in lines if l.lstrip().startswith("{")) == 1
+        lp, e, s = (np.load(out / f"{n}.npy") for n in ("log_psi", "e_loc", "sums"))
+        assert lp.shape == (10000, 2) and lp.dtype == np.float32 and e.shape == (10000, 2) and e.dtype == np.float64
+        assert s.shape == (4,) and s[0] / s[3] == d["config"]["energy"] and np.isfinite(lp).all() and np.isfinite(e).all()
+        runs.append((lp, e, s))
+    (lp0, e0, s0), (lp1, e1, s1) = runs
+    assert np.allclose(lp0, lp1, rtol=0, atol=1e-5) and np.allclose(e0, e1, rtol=1e-9, atol=1e-9)
+    assert np.allclose(s0, s1, rtol=1e-9, atol=0)

@@ -12,6 +12,13 @@ from conftest import GOLDEN, PKG
 LIH_DIR = os.path.join(GOLDEN, "molecules", "LiH")
 
 
+def _on_the_cpu(monkeypatch):
+    """The runs below use the oracle-backed stand-in for the kernels (host tensors): on a host with a GPU as well, the
+    harness must not place the network on the device."""
+    import torch
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+
+
 def test_load_molecule_reads_hdf5_and_pkl_without_openfermion_or_h5py():
     from naqs_amd.system import load_molecule
     mol, qh = load_molecule(LIH_DIR, verbose=False)
@@ -68,6 +75,7 @@ def test_cli_end_to_end_on_lih(tmp_path, monkeypatch, capsys):
     import oracle_backend
     from experiments import _base
     oracle_backend.install(monkeypatch)
+    _on_the_cpu(monkeypatch)
     out = str(tmp_path / "run")
     res = _base.run(n_hid=128, argv=["-m", LIH_DIR, "-o", out, "-single_phase", "-n_hid", "16", "-n_hid_phase", "32",
                                      "-n_layer_phase", "2", "-n_samps", "100000", "-n_unq_samps_min", "10",
@@ -92,6 +100,7 @@ def test_cli_rejects_out_of_scope_options(tmp_path, monkeypatch):
     import oracle_backend
     from experiments import _base
     oracle_backend.install(monkeypatch)
+    _on_the_cpu(monkeypatch)
     with pytest.raises(NotImplementedError):
         _base.run(argv=["-m", LIH_DIR, "-o", str(tmp_path), "-n_lut", "2"])
     with pytest.raises(Exception):
@@ -105,6 +114,7 @@ def test_farm_mode_gives_each_rank_its_own_molecule(tmp_path, monkeypatch, capsy
     import oracle_backend
     from experiments import _base
     oracle_backend.install(monkeypatch)
+    _on_the_cpu(monkeypatch)
     mols = ",".join(os.path.join(GOLDEN, f"ham_{m}.npz") for m in ("LiH", "H2O"))
     common = ["--farm", "-m", mols, "-o", str(tmp_path), "-single_phase", "-n_hid", "8", "-n_hid_phase", "8",
               "-n_samps", "20000", "-n_unq_samps_min", "10", "-n_train", "4", "-lr", "0.001", "-s", "3"]
@@ -145,6 +155,7 @@ def test_cli_runs_the_live_options_no_published_script_uses(extra, suffix, tmp_p
     import oracle_backend
     from experiments import _base
     oracle_backend.install(monkeypatch)
+    _on_the_cpu(monkeypatch)
     out = str(tmp_path / "run")
     res = _base.run(argv=["-m", LIH_DIR, "-o", out, "-n_hid", "16", "-n_samps", "20000", "-n_unq_samps_min", "10",
                           "-n_train", "6", "-lr", "0.001", "-s", "5"] + extra)

@@ -8,10 +8,10 @@ HASH=$(python -c "import sys; sys.path.insert(0, 'naqs-for-quantum-chemistry_amd
 echo "library source hash: $HASH" | tee $G/source_hash.txt
 timeout 1500 python -m pytest tests -m gpu -q --timeout=300 > $G/pytest.log 2>&1; tail -3 $G/pytest.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $G/smoke.log 2>&1; tail -2 $G/smoke.log
-timeout 600 python bench.py > $G/bench.log 2> $G/bench.err
-timeout 600 python bench.py --steps 20 --warmup 5 > $G/bench_driver_like.log 2>/dev/null
-timeout 600 python bench.py --shard rows --molecule Li2O --samples 50000 --steps 100 --warmup 10 > $G/bench_li2o.log 2>/dev/null
-NAQS_BENCH_FORCE_DIST=1 timeout 600 python bench.py --gpus 1 --steps 100 --warmup 10 --no-cpu-baseline > $G/bench_dist1.log 2>/dev/null
+timeout 600 python bench.py --full > $G/bench.log 2> $G/bench.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $G/bench_driver_like.log 2>/dev/null
+timeout 600 python bench.py --full --shard rows --molecule Li2O --samples 50000 --steps 100 --warmup 10 > $G/bench_li2o.log 2>/dev/null
+NAQS_BENCH_FORCE_DIST=1 timeout 600 python bench.py --full --gpus 1 --steps 100 --warmup 10 --no-cpu-baseline > $G/bench_dist1.log 2>/dev/null
 timeout 600 python bench.py --emulate-world 1,2,4,8 --molecule Li2O --samples 50000 --steps 100 --warmup 10 > $G/emulate_li2o.log 2>/dev/null
 timeout 600 python tools/scaling_model.py tests/golden/ham_N2.npz 300 $G/train_scaling_n2.json > $G/train_scaling_n2.log 2>&1
 NAQS_SCALING_PUBLISHED=1 NAQS_SCALING_TRAIN_FIRST=30 timeout 600 python tools/scaling_model.py tests/golden/ham_Li2O.npz 60 $G/train_scaling_li2o_pub.json > $G/train_scaling_li2o_pub.log 2>&1
