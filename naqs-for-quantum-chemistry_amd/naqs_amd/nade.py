@@ -228,7 +228,7 @@ class OrbitalNADE(nn.Module):
         [B, N/2, 4, 2] (nade.py:738-770)."""
         if x.dim() < 2:
             x = x.unsqueeze(0)
-        x = x.to(self.device, torch.float32)
+        x = x.to(self.device, next(self.parameters()).dtype)         # float32 networks; a float64 copy is the tests' reference
         B, P = x.shape[0], self.P
         a, b = x[:, 0::2], x[:, 1::2]                        # alpha / beta occupations per block
         bits_a, bits_b = (a > 0).long(), (b > 0).long()

@@ -137,7 +137,7 @@ class NAQSComplex_NADE_orbitals:
 
     def _evaluate_model(self, s):
         self.model.predict()
-        x = s.to(self.device)[..., self._q2m].float()
+        x = s.to(self.device)[..., self._q2m].to(self.param_list()[0].dtype)
         return self.model(x)[:, self._m2s_shell]
 
     def _evaluate_log_psi(self, s, gather_state=True):

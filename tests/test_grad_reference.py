@@ -1,0 +1,96 @@
+"""The float64 reference of the training backward (tests/grad_reference.py) pinned to the reference's own vectors: a float64
+copy of every ``nade_*.npz`` network reproduces the recorded loss and gradients of _SGD_step, and float32 networks are
+untouched by the modules following their parameters' dtype.  test_backward_gpu.py holds the HIP backward to this reference."""
+import glob
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import grad_reference as gr
+from conftest import GOLDEN, golden
+
+FIXTURES = sorted(os.path.basename(f)[5:-4] for f in glob.glob(os.path.join(GOLDEN, "nade_*.npz")))
+
+
+def test_every_fixture_is_listed():
+    assert len(FIXTURES) == 16 and "N2" in FIXTURES and "CH2_noampsym" in FIXTURES
+
+
+@pytest.mark.parametrize("fix", FIXTURES)
+def test_f64_modules_reproduce_reference_loss_and_gradients(fix):
+    """loss = 2 Re sum_i w_i log psi_i (E_i - <E>)^* on the reference's sampled states with its E_loc (energy.py:328-329),
+    autograd in float64: the recorded sgd_loss and grad:* to 2e-3 of each tensor's scale (the reference ran in float32)."""
+    z = golden(f"nade_{fix}.npz")
+    hil, wf = gr.f64_copy(fix)
+    assert all(p.dtype == torch.float64 for p in wf.model.parameters())
+    s = torch.tensor(z["samp_states"])
+    lp, margin = gr.log_psi_and_kink_margin(wf, s)
+    assert lp.dtype == torch.float64 and margin.shape == (len(s),) and np.all(margin >= 0)
+    assert np.max(np.abs(lp.detach().numpy() - z["samp_log_psi"])) < 5e-5
+    w = z["samp_counts"].astype(np.float64)
+    w /= w.sum()
+    e = z["sgd_eloc_c128"]
+    d = e - (w * e).sum()
+    loss = 2 * (torch.as_tensor(w) * (lp[:, 0] * torch.as_tensor(d.real) - lp[:, 1] * torch.as_tensor(d.imag))).sum()
+    assert abs(loss.item() - float(z["sgd_loss"])) < 1e-4 * max(1, abs(float(z["sgd_loss"])))
+    got = gr.grad_f64(wf, s, gr.loss_grad_f64(e, w), lp=lp)
+    for name, p in wf.model.named_parameters():
+        g_ref = z["grad:" + name]
+        scale = max(1e-3, np.abs(g_ref).max())
+        assert np.max(np.abs(got[name] - g_ref)) < 2e-3 * scale, (name, np.max(np.abs(got[name] - g_ref)) / scale)
+
+
+def test_float32_networks_are_unchanged():
+    """The float32 copy built by f64_copy(dtype=float32) and the fixture's own float32 network give the same bits."""
+    from test_nade import make_wf
+    z = golden("nade_N2.npz")
+    _, wf = make_wf("N2", z)
+    _, wf32 = gr.f64_copy(wf, dtype=torch.float32)
+    s = torch.tensor(z["samp_states"][:500])
+    with torch.no_grad():
+        a = wf.log_psi(s)
+        b = wf32.log_psi(s)
+    assert a.dtype == torch.float32 and torch.equal(a, b)
+
+
+def test_loss_gradient_helpers():
+    rs = np.random.RandomState(0)
+    M = 1000
+    e = rs.normal(-107.4, 0.5, M) + 1j * rs.normal(0, 1e-3, M)
+    w = rs.uniform(0.5, 1.5, M)
+    w /= w.sum()
+    g64 = gr.loss_grad_f64(e, w)
+    sums = np.array([(w * e.real).sum(), (w * e.imag).sum(), (w * e.real ** 2).sum(), w.sum()])
+    g32 = gr.loss_grad_f32_emulated(e, w, sums)
+    assert g32.dtype == np.float32
+    assert np.max(np.abs(g32 - g64)) < 1e-7 and np.max(np.abs(g64)) > 1e-4
+    assert abs(g64[:, 0].sum()) < 1e-12                             # sum_i w_i (E_i - <E>) = 0
+    g, n = gr.kink_free(g64, np.r_[np.zeros(3), np.ones(M - 3)])
+    assert n == 3 and not g[:3].any() and np.array_equal(g[3:], g64[3:])
+
+
+def test_kink_margin_sees_every_relu():
+    """The margin is the smallest |ReLU input| over the amplitude blocks (torch.relu) AND the phase MLP (nn.ReLU)."""
+    relu = torch.relu
+    hil, wf = gr.f64_copy("N2")
+    s = torch.tensor(golden("nade_N2.npz")["samp_states"][:64])
+    lp, margin = gr.log_psi_and_kink_margin(wf, s)
+    phase0 = wf.model.phase_layers[0].layers[0][0]                # nn.Linear -> nn.ReLU of the phase MLP
+    amp0 = wf.model.amp_layers[0].layers[0][0]                      # block 0 sees a zero input: its pre-activation is its bias
+    with torch.no_grad():
+        b_ph, b_amp = phase0.bias.clone(), amp0.bias.clone()
+        # a phase unit whose pre-activation is exactly zero for row 0: that row's margin drops to 0
+        x = s[:1].to(torch.float64)[..., wf._q2m]
+        P = wf.model.P
+        xin = torch.cat([x[:, 0:2 * (P - 1):2], x[:, 1:2 * (P - 1):2]], -1)
+        phase0.bias[0] = -(xin @ phase0.weight[0])[0]
+        _, m_ph = gr.log_psi_and_kink_margin(wf, s)
+        phase0.bias.copy_(b_ph)
+        amp0.bias[3] = 0.0                                          # a zero pre-activation in every row (torch.relu)
+        _, m_amp = gr.log_psi_and_kink_margin(wf, s)
+        amp0.bias.copy_(b_amp)
+    assert m_ph[0] < 1e-12 < margin[0] and np.all(margin > 0)
+    assert np.all(m_amp == 0)
+    assert torch.relu is relu                                       # (the wrapper is gone again)

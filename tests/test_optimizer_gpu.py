@@ -31,6 +31,9 @@ def make_opt_gpu(mol, tmp, **kw):
 
 @pytest.mark.parametrize("mol", ["LiH", "H2O", "N2"])
 def test_sgd_step_matches_reference_step_on_device(mol, tmp_path):
+    """One _SGD_step against the reference's: E, Var and the parameters after one Adam step.  With eps = 1e-15 that step is
+    lr * sign(g), so this pins the gradient's SIGN pattern only; its magnitudes are held to the reference's grad:* and to
+    float64 by test_backward_gpu.py (test_training_step_gradients_match_reference, test_backward_against_float64_at_every_size_class)."""
     z, hil, wf, opt = make_opt_gpu(mol, tmp_path)
     states = torch.tensor(z["samp_states"], device="cuda")
     counts = torch.tensor(z["samp_counts"], device="cuda")

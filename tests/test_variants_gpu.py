@@ -73,6 +73,9 @@ def test_fused_family_log_psi_matches_reference(fix):
 
 @pytest.mark.parametrize("fix", FUSED + EAGER)
 def test_sgd_step_matches_reference_step_on_device(fix, tmp_path, capsys):
+    """One _SGD_step against the reference's: E, Var and the parameters after one Adam step.  With eps = 1e-15 that step is
+    lr * sign(g), so this pins the gradient's SIGN pattern only; its magnitudes are held to the reference's grad:* and to
+    float64 by test_backward_gpu.py (test_training_step_gradients_match_reference, test_backward_against_float64_at_every_size_class)."""
     mol, z, hil, wf = _wf(fix)
     opt = _opt(mol, wf, tmp_path)
     from naqs_amd.flat_adam import FlatAdam
