@@ -273,7 +273,8 @@ int naqs_net_spec_counts(const naqs_net_t *net, int64_t counts[2]);
  * turns (may be NULL) <- sampler calls of this handle so far that had to wait for another handle's turn to end.
  * The samples do not depend on the switch. */
 int naqs_net_share_device(naqs_net_t *net, int on, int64_t *turns);
-/* Name of the log-psi kernel the most recent naqs_net_logpsi / naqs_logpsi_eloc / training forward launched. */
+/* Name of the log-psi kernel the most recent naqs_net_logpsi / naqs_logpsi_eloc / training forward launched, followed by
+ * " + <kernel>" for the amplitude launch in front of it (or the aggregate-phase launches). */
 int naqs_net_last_kernel(const naqs_net_t *net, char *buf, int buf_len);
 
 

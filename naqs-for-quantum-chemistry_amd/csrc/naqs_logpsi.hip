@@ -2579,12 +2579,14 @@ int naqs::net_amp_forward(naqs_net *net, int64_t M, const uint64_t *keys_dev, hi
         const int64_t waves = (M + AMPK_TG * 16 - 1) / (AMPK_TG * 16) * d.P;
         const unsigned grid = (unsigned)((waves + AMPK_WAVES - 1) / AMPK_WAVES);
         const size_t lds = 0;
+        std::snprintf(net->last_amp, sizeof(net->last_amp), "amp_mfma_kernel<%d>", d.Ha == 128 ? 8 : (d.Ha == 64 ? 4 : 2));
         if (d.Ha == 128) NAQS_KLAUNCH(amp_mfma_kernel<8>, dim3(grid), dim3(AMPK_WAVES * 64), lds, s, d, net->d_wamp, M, keys_dev, net->d_scratch, feed ? *feed : none);
         else if (d.Ha == 64) NAQS_KLAUNCH(amp_mfma_kernel<4>, dim3(grid), dim3(AMPK_WAVES * 64), lds, s, d, net->d_wamp, M, keys_dev, net->d_scratch, feed ? *feed : none);
         else NAQS_KLAUNCH(amp_mfma_kernel<2>, dim3(grid), dim3(AMPK_WAVES * 64), lds, s, d, net->d_wamp, M, keys_dev, net->d_scratch, feed ? *feed : none);
         HIP_TRY(hipGetLastError());
         return NAQS_OK;
     }
+    std::snprintf(net->last_amp, sizeof(net->last_amp), "amp_kernel");
     return launch_amp_kernel(d, net->d_w, M, keys_dev, net->d_scratch, feed ? *feed : none, 0, s);
 }
 
@@ -2605,13 +2607,16 @@ static int agg_logpsi(naqs_net *net, int64_t M, const uint64_t *keys_dev, float 
         NAQS_KLAUNCH(amp2_kernel, dim3((unsigned)((M + AMP_TILES * WAVE - 1) / (AMP_TILES * WAVE)), (unsigned)d0.P, 2),
                            dim3(AMP_TILES * AMP_SPLIT * WAVE), lds, s, d0, net->d_w, net->d_scratch, feed, d1, net->d_wph, s_ph, M, keys_dev);
         HIP_TRY(hipGetLastError());
+        std::snprintf(net->last_kernel, sizeof(net->last_kernel), "amp2_kernel + agg_finish_kernel");
     } else {
         if (mfma_amp) st = naqs::net_amp_forward(net, M, keys_dev, s, &feed);
         else {                                             // the VALU form, like the merged launch (same numbers)
             st = naqs::net_amp_forward(net, M, keys_dev, s, nullptr, /*launch=*/false);
             if (st == NAQS_OK) st = launch_amp_kernel(net->dims, net->d_w, M, keys_dev, net->d_scratch, feed, 0, s);
+            std::snprintf(net->last_amp, sizeof(net->last_amp), "amp_kernel");
         }
         if (st != NAQS_OK) return st;
+        std::snprintf(net->last_kernel, sizeof(net->last_kernel), "%s + amp_kernel(raw) + agg_finish_kernel", net->last_amp);
         s_ph = net->d_scratch + (size_t)net->dims.P * net->cap_M;
         const ElocFeed none{};
         if (prof) { st = net->prof.begin(s); if (st != NAQS_OK) return st; }
@@ -2771,6 +2776,10 @@ int naqs::net_logpsi_impl(naqs_net *net, int64_t M, const uint64_t *keys_dev, fl
     else if (use_h) std::snprintf(net->last_kernel, sizeof(net->last_kernel), "phase_kernel_h<RB=%d, SAVE=%d, FMT=%d (%s)>%s", rb, save.x != nullptr ? 1 : 0,
                              fmt, fmt == 2 ? "f16x2" : "bf16x3", amp_in_phase ? " incl. amplitude prologue" : "");
     else std::snprintf(net->last_kernel, sizeof(net->last_kernel), "phase_kernel<RB=%d> (f32 MFMA)", rb);
+    if (!amp_in_phase) {                                   // (the amplitude launch net_amp_forward made in front)
+        const size_t n = std::strlen(net->last_kernel);
+        std::snprintf(net->last_kernel + n, sizeof(net->last_kernel) - n, " + %s", net->last_amp);
+    }
     if (wt) {
     } else if (ws) {
         const size_t lds = rb * lds_h16 + (size_t)d.P * bm * 8 * sizeof(float);
@@ -2903,7 +2912,7 @@ NAQS_API int naqs_net_prof_read(naqs_net_t *net, double *total_ms, int64_t *laun
 
 NAQS_API int naqs_net_last_kernel(const naqs_net_t *net, char *buf, int buf_len) {
     if (!net || !buf || buf_len <= 0) return NAQS_ERR_INVALID;
-    std::snprintf(buf, (size_t)buf_len, "%s", net->aggregate ? "amp_mfma_kernel + amp_kernel(raw) + agg_finish_kernel" : net->last_kernel);
+    std::snprintf(buf, (size_t)buf_len, "%s", net->last_kernel);
     return NAQS_OK;
 }
 

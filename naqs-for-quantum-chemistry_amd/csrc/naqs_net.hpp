@@ -301,7 +301,8 @@ struct naqs_net {
     naqs::EventRing prof;                   // HIP-event brackets around the log-psi kernel (naqs_net_prof_*)
     naqs::EventRing prof_samp;              // ... around the sampler's launches of a training step (naqs_net_prof_select(net, 1))
     int prof_which = 0;
-    char last_kernel[96] = {0};             // naqs_net_last_kernel
+    char last_kernel[192] = {0};            // naqs_net_last_kernel: the phase kernel (+ the amplitude / aggregate launches)
+    char last_amp[32] = {0};                // the amplitude kernel net_amp_forward launched last
     int64_t *h_info = nullptr;              // mapped host words the sampler publishes (M, overflow, call sequence number) to
     int64_t *d_info_alias = nullptr;        // their device address
     int64_t *d_info2 = nullptr;             // device words for the sampler's plain (M, overflow) output of those calls

@@ -628,9 +628,10 @@ class FusedLogPsi:
         return ms.value, n.value
 
     def last_kernel(self):
-        """Name (with template arguments) of the kernel the most recent call launched (measurement aid)."""
-        buf = ctypes.create_string_buffer(128)
-        _lib.check(self._lib.naqs_net_last_kernel(self._h, buf, 128), "naqs_net_last_kernel")
+        """Name (with template arguments) of the kernel the most recent log-psi call launched, followed by the amplitude or
+        aggregate-phase launches that went with it (" + amp_mfma_kernel<4>"); measurement aid and dispatch check."""
+        buf = ctypes.create_string_buffer(256)
+        _lib.check(self._lib.naqs_net_last_kernel(self._h, buf, 256), "naqs_net_last_kernel")
         return buf.value.decode()
 
     def share_device(self, on=None):

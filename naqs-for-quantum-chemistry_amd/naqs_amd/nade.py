@@ -346,7 +346,7 @@ class OrbitalNADE(nn.Module):
         with ret_output the teacher-forced log psi [U, 2] is appended (no gradients here — call
         ``forward`` on the returned states for the differentiable value)."""
         dev = self.device
-        states = torch.zeros((1, 0), device=dev)
+        states = torch.zeros((1, 0), device=dev, dtype=self._blockidx2spin.dtype)     # (the parameters' dtype: float32, or float64 in tests)
         counts = torch.tensor([int(batch_size)], dtype=torch.float64, device=dev)
         probs = torch.ones(1, dtype=torch.float32, device=dev)
         for n in range(self.P):

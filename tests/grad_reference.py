@@ -10,7 +10,9 @@ on the CPU is an exact-arithmetic stand-in for what the HIP backward computes in
 * ``loss_grad_f64`` / ``loss_grad_f32_emulated``
                                d loss / d (log|psi|, phase) of the VMC loss of _SGD_step (energy.py:328-329): exactly, and in
                                the float32 arithmetic vmc_grad_kernel documents (naqs_grad.hip);
-* ``kink_free``                g with the rows near a kink zeroed.
+* ``kink_free``                g with the rows near a kink zeroed;
+* ``log_psi_f64``              the forward alone, in chunks of rows (no graph): float64 numpy [M, 2];
+* ``sorted_rows``              the first m rows of a key set in the library's (ascending) order, with their reference rows.
 """
 import contextlib
 
@@ -130,3 +132,22 @@ def _complex(eloc):
     if np.iscomplexobj(e):
         return e.astype(np.complex128)
     return e[..., 0].astype(np.float64) + 1j * e[..., 1].astype(np.float64)
+
+
+def log_psi_f64(wf, states, chunk=4096):
+    """log psi [M, 2] of ``states`` ([M, N] +-1, qubit order) through the network ``wf`` (an ``f64_copy``: float64, or float32
+    for the CPU float32 error it is compared with), as float64 numpy.  The forward is row-independent: chunks of rows give
+    the same numbers as one pass and bound the memory of the [512, 512] networks."""
+    states = torch.as_tensor(states)
+    out = np.empty((states.shape[0], 2), np.float64)
+    with torch.no_grad():
+        for lo in range(0, states.shape[0], chunk):
+            out[lo:lo + chunk] = wf.log_psi(states[lo:lo + chunk]).reshape(-1, 2).double().numpy()
+    return out
+
+
+def sorted_rows(keys, m, *tables):
+    """keys: the key set a reference was computed on, in its own order; -> (its first m keys ascending — the order the
+    library's tables are kept in —, then each table's rows in that order)."""
+    order = np.argsort(keys[:m], kind="stable")
+    return (keys[:m][order],) + tuple(t[:m][order] for t in tables)

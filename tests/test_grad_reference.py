@@ -1,6 +1,7 @@
 """The float64 reference of the training backward (tests/grad_reference.py) pinned to the reference's own vectors: a float64
 copy of every ``nade_*.npz`` network reproduces the recorded loss and gradients of _SGD_step, and float32 networks are
-untouched by the modules following their parameters' dtype.  test_backward_gpu.py holds the HIP backward to this reference."""
+untouched by the modules following their parameters' dtype.  test_backward_gpu.py holds the HIP backward to this reference,
+test_forward_f64_gpu.py the HIP forward and the sampler's probabilities."""
 import glob
 import os
 
@@ -94,3 +95,42 @@ def test_kink_margin_sees_every_relu():
     assert m_ph[0] < 1e-12 < margin[0] and np.all(margin > 0)
     assert np.all(m_amp == 0)
     assert torch.relu is relu                                       # (the wrapper is gone again)
+
+
+@pytest.mark.parametrize("fix", FIXTURES)
+def test_f64_forward_reproduces_reference_log_psi(fix):
+    """log_psi_f64 (chunked, float64) of the reference's eval_states against its recorded float32 eval_log_psi: the recorded
+    values differ from float64 by float32 rounding only, within the bounds test_forward_f64_gpu.py holds the HIP forward to
+    (log|psi|: 2e-6 + 2e-7 |log|psi||, measured <= 1.3e-6; phase: 5e-6 max |phase|, measured <= 5.3e-7).  Chunks of 7 rows
+    give one pass's numbers to float64 rounding (the GEMMs block differently)."""
+    z = golden(f"nade_{fix}.npz")
+    hil, wf = gr.f64_copy(fix)
+    s = torch.tensor(z["eval_states"])
+    lp = gr.log_psi_f64(wf, s)
+    assert lp.dtype == np.float64 and lp.shape == (len(s), 2)
+    assert np.max(np.abs(gr.log_psi_f64(wf, s, chunk=7) - lp)) < 1e-12
+    ref = z["eval_log_psi"].astype(np.float64)
+    assert np.array_equal(np.isfinite(lp), np.isfinite(ref))
+    fin = np.isfinite(ref[:, 0])
+    d = np.abs(lp - ref)
+    assert np.all(d[fin, 0] <= 2e-6 + 2e-7 * np.abs(ref[fin, 0])), d[fin, 0].max()
+    assert np.all(d[:, 1] <= 5e-6 * max(1e-3, np.abs(lp[:, 1]).max())), d[:, 1].max()
+
+
+def test_sorted_rows():
+    keys = np.array([9, 3, 7, 1, 5], np.uint64)
+    t = np.arange(10.0).reshape(5, 2)
+    k, r = gr.sorted_rows(keys, 4, t)
+    assert k.tolist() == [1, 3, 7, 9] and r[:, 0].tolist() == [6, 2, 4, 0]
+
+
+@pytest.mark.parametrize("fix", ["N2", "N2_nomask", "N2_aggphase", "LiH_fullmask", "LiH_phasesym_agg"])
+def test_sampler_probs_are_psi_squared_in_float64(fix):
+    """The identity test_forward_f64_gpu.py's sampler check rests on: the probs of the torch sampler (_forward_sample: the
+    product over pairs of the conditional |amplitude|^2, nade.py:351-365) are exp(2 log|psi|) of the drawn states — with
+    PARTIAL, NONE and FULL masking and the aggregate phase — to float64 rounding."""
+    hil, wf = gr.f64_copy(fix)
+    states, counts, probs = wf.sample(100000, ret_log_psi=False, use_fused=False, generator=torch.Generator().manual_seed(5))
+    assert probs.dtype == torch.float64 and len(probs) > 200 and counts.sum() > 0
+    want = np.exp(2 * gr.log_psi_f64(wf, states)[:, 0])
+    assert np.max(np.abs(probs.numpy() / want - 1)) < 1e-13
