@@ -196,9 +196,10 @@ int naqs_prof_stride(naqs_ham_t *h, int stride);
  * Fused log-psi evaluation of the orbital NADE (inference; gradients stay with PyTorch autograd).
  * Replaces wavefunction.log_psi(states) (src/naqs/wavefunction.py:167-183) ->
  * _forward_predict (src/naqs/network/nade.py:738-770) for the published architecture family:
- * one amplitude MLP per orbital pair (one hidden layer), and either a single phase MLP on the last pair
- * (aggregate_phase = False: -single_phase, the published runs) or one single-hidden-layer phase block per pair whose
- * outputs are summed (aggregate_phase = True: the reference's default); SoftmaxLogProbAmps amplitudes, no phase symmetry.
+ * one amplitude MLP per orbital pair (one hidden layer; 2..4 of one width through naqs_net_create_amp_layers), and either
+ * a single phase MLP on the last pair (aggregate_phase = False: -single_phase, the published runs) or one single-hidden-layer
+ * phase block per pair whose outputs are summed (aggregate_phase = True: the reference's default); SoftmaxLogProbAmps
+ * amplitudes, no phase symmetry.
  * ============================================================================================== */
 typedef struct naqs_net naqs_net_t;
 
@@ -210,7 +211,7 @@ typedef struct naqs_net_config {
     int32_t n_alpha, n_beta;          /* electron budget of the masks (nade.py:417-474); -1/-1: unrestricted */
     int32_t masking;                  /* NadeMasking: 0 NONE, 1 PARTIAL, 2 FULL (network/base.py:20-23) */
     int32_t use_amp_spin_sym;         /* 1: 5 amplitude outputs + symmetrisation (nade.py:576-594) */
-    int32_t amp_hidden;               /* width of the single hidden layer of every amplitude block */
+    int32_t amp_hidden;               /* width of every hidden layer of every amplitude block */
     int32_t n_phase_hidden;           /* hidden layers of the phase block (>= 1) */
     int32_t phase_hidden[NAQS_NET_MAX_PHASE_LAYERS];   /* their widths */
     int32_t qubit2model[2 * NAQS_NET_MAX_PAIRS];       /* model position -> qubit (wavefunction.py:56-83, :369-383) */
@@ -226,6 +227,15 @@ typedef struct naqs_net_config {
 } naqs_net_config_t;
 
 int naqs_net_create(const naqs_net_config_t *cfg, int device, naqs_net_t **out);
+/* naqs_net_create for amplitude blocks of n_amp_hidden hidden layers, all cfg->amp_hidden wide (a multiple of 16, <= 128):
+ * the reference's -n_layer (experiments/run.py; nade.py builds each block as n_layer Linear + ReLU groups and an output Linear).
+ * n_amp_hidden == 1 is naqs_net_create.  NAQS_ERR_INVALID: n_amp_hidden outside 1..4; NAQS_ERR_UNSUPPORTED: aggregate_phase = 1
+ * with n_amp_hidden > 1, or another width.  The flat layout stays the state_dict order, block by block
+ * (amp_layers.<n>.layers.0.0.weight, .bias, amp_layers.<n>.layers.1.0.weight, ..., the output Linear), then the phase layers.
+ * Every naqs_net_* / naqs_vmc_* entry point takes such a handle; the deep blocks run in launches of their own (the log-amplitude
+ * launch in front of the phase kernel, one expand + scatter launch pair per sampler level, their own backward launch), so
+ * naqs_vmc_step / naqs_vmc_run take the non-speculative order for them. */
+int naqs_net_create_amp_layers(const naqs_net_config_t *cfg, int32_t n_amp_hidden, int device, naqs_net_t **out);
 int naqs_net_destroy(naqs_net_t *net);
 /* Number of float parameters expected by naqs_net_set_weights: the reference's state_dict order,
  * flattened (amp_layers.0.layers.0.0.weight, .bias, amp_layers.0.layers.1.0.weight, .bias, ...,
@@ -274,7 +284,9 @@ int naqs_net_spec_counts(const naqs_net_t *net, int64_t counts[2]);
  * The samples do not depend on the switch. */
 int naqs_net_share_device(naqs_net_t *net, int on, int64_t *turns);
 /* Name of the log-psi kernel the most recent naqs_net_logpsi / naqs_logpsi_eloc / training forward launched, followed by
- * " + <kernel>" for the amplitude launch in front of it (or the aggregate-phase launches). */
+ * " + <kernel>" for the amplitude launch in front of it (or the aggregate-phase launches).  Handles of
+ * naqs_net_create_amp_layers append "; sampler: ..." or "; backward: ..." for the deep launches of the most recent sampler or
+ * amplitude-backward call. */
 int naqs_net_last_kernel(const naqs_net_t *net, char *buf, int buf_len);
 
 

@@ -16,10 +16,12 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstdint>
 
 #include "naqs_common.hpp"
 #include "naqs_net.hpp"
+#include "naqs_amp_deep.hpp"
 #include "naqs_amp_backward.hpp"
 
 namespace {
@@ -52,6 +54,19 @@ __global__ __launch_bounds__(512) void amp_backward_kernel(const NetDims d, cons
     const int n = blockIdx.y;
     float *out = partial + (int64_t)blockIdx.x * partial_stride + src.off[n];
     naqs::ampbw::pair_dispatch(n, d, w, M, keys, g, out, smem, raw, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// deep amplitude blocks (naqs_net_create_amp_layers): workgroup = pair blockIdx.y x a strided set of 64-sample tiles, partial sums
+// per workgroup in state_dict order like amp_backward_kernel's (naqs_amp_deep.hpp: amp_deep_backward_pair)
+template <int CT>
+__global__ __launch_bounds__(naqs::DBW * 64) void amp_deep_backward_kernel(const NetDims d, const float *__restrict__ wdeep, const naqs::DeepAmp da,
+                                                                         const int64_t M, const uint64_t *__restrict__ keys,
+                                                                         const float *__restrict__ g, float *__restrict__ partial,
+                                                                         const int64_t partial_stride) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int n = blockIdx.y;
+    float *out = partial + (int64_t)blockIdx.x * partial_stride + (da.src[n] - da.src[0]);
+    naqs::amp_deep_backward_pair<CT>(d, wdeep + da.off[n], da.L, n, M, keys, g, out, smem, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // aggregate_phase: the amplitude blocks (blockIdx.z == 0, on g[:, 0]) and the per-pair phase blocks (1, raw, on g[:, 1]) in ONE
@@ -249,19 +264,38 @@ int naqs::net_blocks_backward(naqs_net *net, const NetDims &d, const float *w, c
         HIP_TRY(hipMalloc((void **)&net->d_gpart, 2 * (size_t)MAX_TILE_WGS * stride * sizeof(float)));
     }
     float *gpart = net->d_gpart + (slot ? (size_t)MAX_TILE_WGS * stride : 0);
-    const int NW = d.Ha >> 4;
-    const size_t lds = naqs::ampbw::smem_floats(d) * sizeof(float);
-    if (lds > 156 * 1024) return NAQS_ERR_UNSUPPORTED;
-    if (!net->grad_attr_set) {
-        const int lds_max = 156 * 1024;
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&amp_backward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-        net->grad_attr_set = true;
+    if (net->amp_depth > 1 && raw == 0 && &d == &net->dims) {       // deep amplitude blocks
+        const size_t lds_d = naqs::deep_bw_smem_floats(d.Ha, net->amp_depth) * sizeof(float);
+        if (lds_d > 156 * 1024) return NAQS_ERR_UNSUPPORTED;
+        const naqs::DeepAmp da = naqs::deep_amp(net);
+        switch (d.Ha >> 4) {
+#define NAQS_DEEP(C) case C:                                                                                                              \
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&amp_deep_backward_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024)); \
+            NAQS_KLAUNCH(amp_deep_backward_kernel<C>, dim3((unsigned)n_wg, (unsigned)d.P), dim3(naqs::DBW * WAVE), lds_d, s, d, net->d_wdeep, da, M, \
+                         keys_dev, g_dev, gpart, stride);                                                                                 \
+            break;
+            NAQS_DEEP(1) NAQS_DEEP(2) NAQS_DEEP(3) NAQS_DEEP(4) NAQS_DEEP(5) NAQS_DEEP(6) NAQS_DEEP(7) NAQS_DEEP(8)
+#undef NAQS_DEEP
+            default: return NAQS_ERR_UNSUPPORTED;
+        }
+        HIP_TRY(hipGetLastError());
+        std::snprintf(net->last_deep, sizeof(net->last_deep), "backward: amp_deep_backward_kernel<%d, L=%d>", d.Ha >> 4,
+                      net->amp_depth);
+    } else {
+        const int NW = d.Ha >> 4;
+        const size_t lds = naqs::ampbw::smem_floats(d) * sizeof(float);
+        if (lds > 156 * 1024) return NAQS_ERR_UNSUPPORTED;
+        if (!net->grad_attr_set) {
+            const int lds_max = 156 * 1024;
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&amp_backward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+            net->grad_attr_set = true;
+        }
+        AmpSrc src;
+        for (int n = 0; n < MAXP; ++n) src.off[n] = src_off[n] - src_off[0];         // relative to this set's first parameter
+        NAQS_KLAUNCH(amp_backward_kernel, dim3((unsigned)n_wg, (unsigned)d.P), dim3((unsigned)(NW * WAVE)), lds, s, d, w, M, keys_dev,
+                           g_dev, gpart, stride, src, raw);
+        HIP_TRY(hipGetLastError());
     }
-    AmpSrc src;
-    for (int n = 0; n < MAXP; ++n) src.off[n] = src_off[n] - src_off[0];         // relative to this set's first parameter
-    NAQS_KLAUNCH(amp_backward_kernel, dim3((unsigned)n_wg, (unsigned)d.P), dim3((unsigned)(NW * WAVE)), lds, s, d, w, M, keys_dev,
-                       g_dev, gpart, stride, src, raw);
-    HIP_TRY(hipGetLastError());
     if (defer) {
         defer->count = n_block_params; defer->stride = stride; defer->n_partials = n_wg; defer->partial = gpart;
         return NAQS_OK;
@@ -278,6 +312,7 @@ int naqs::net_blocks_backward(naqs_net *net, const NetDims &d, const float *w, c
 int naqs::net_blocks_backward_plan(naqs_net *net, const NetDims &d, const int64_t *src_off, int64_t n_block_params, int64_t M, int slot,
                                    BlockReduceJob *job, naqs::ampbw::AmpSrc *src) {
     if (d.Ha > 128 || (d.Ha & 15) || M <= 0 || !job || !src) return NAQS_ERR_INVALID;
+    if (net->amp_depth > 1 && &d == &net->dims) return NAQS_ERR_UNSUPPORTED;       // (deep blocks: net_blocks_backward's own launch)
     const int n_wg = (int)std::min<int64_t>(MAX_TILE_WGS, (M + GT - 1) / GT);
     const int64_t stride = (std::max(net->amp_params, net->ph_params) + 3) & ~3ll;
     if (!net->d_gpart) {

@@ -34,6 +34,7 @@
 #include "naqs_hash.hpp"
 #include "naqs_net.hpp"
 #include "naqs_amp_mfma.hpp"
+#include "naqs_amp_deep.hpp"
 #include "naqs_pack.hpp"
 
 namespace {
@@ -936,6 +937,52 @@ __global__ __launch_bounds__(AMPK_WAVES * 64) __attribute__((amdgpu_waves_per_eu
         if (feed.key_bits == 32) naqs::feed_key<uint32_t>(feed, i, key);
         else naqs::feed_key<uint64_t>(feed, i, key);
     }
+}
+
+// Deep amplitude blocks (naqs_net_create_amp_layers): the conditional log-amplitudes of every (row, pair) into the [P][M] scratch,
+// the same contract as amp_mfma_kernel — the phase kernels behind it sum them.  A wave owns one (tile of 16 rows, pair) item
+// (naqs_amp_deep.hpp: amp_deep_item); the waves of pair 0 feed the E_loc hash table.
+constexpr int DEEPK_WAVES = 4;
+template <int CT>
+__global__ __launch_bounds__(DEEPK_WAVES * 64) void amp_deep_kernel(const NetDims d, const float *__restrict__ wdeep, const naqs::DeepAmp da,
+                                                                    const int64_t M, const uint64_t *__restrict__ keys,
+                                                                    float *__restrict__ scratch, const ElocFeed feed) {
+    __shared__ __attribute__((aligned(16))) float s_outs[DEEPK_WAVES][128];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t tiles = (M + 15) / 16;
+    const int64_t item = (int64_t)blockIdx.x * DEEPK_WAVES + wave;
+    if (item >= tiles * d.P) return;                                             // wave-uniform; no barrier below
+    const int n = (int)(item / tiles);
+    const int64_t row0 = (item - (int64_t)n * tiles) * 16;
+    const int64_t i = row0 + (lane & 15);
+    const uint64_t key = i < M ? keys[i] : 0ull;
+    uint32_t a = 0, b = 0;
+    naqs::key_strings(d, key, a, b);
+    float *outs = s_outs[wave];
+    naqs::amp_deep_item<CT>(d, wdeep + da.off[n], da.L, n, a | (b << 16), lane, outs);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (lane < 16 && i < M) {
+        float o[5];
+#pragma unroll
+        for (int c = 0; c < 5; ++c) o[c] = outs[lane * 8 + c];
+        const uint32_t mask = (1u << n) - 1u;
+        const int occ = (int)((a >> n) & 1u) + 2 * (int)((b >> n) & 1u);
+        scratch[(int64_t)n * M + i] = naqs::amp_finish(d, n, o, a & mask, b & mask, occ);
+        if (n == 0 && feed.tab != nullptr) {
+            if (feed.key_bits == 32) naqs::feed_key<uint32_t>(feed, i, key);
+            else naqs::feed_key<uint64_t>(feed, i, key);
+        }
+    }
+}
+
+// the deep blocks' parameters from the flat state_dict vector into d_wdeep: pair blockIdx.y, moved to its 16-byte aligned offset
+__global__ __launch_bounds__(256) void deep_pack_kernel(const float *__restrict__ flat, const naqs::DeepAmp da, const int Ha, const int nout,
+                                                        float *__restrict__ dst) {
+    const int n = blockIdx.y;
+    const int64_t cnt = naqs::deep_pair_floats(Ha, nout, da.L, n);
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < cnt; e += (int64_t)gridDim.x * 256) dst[da.off[n] + e] = flat[da.src[n] + e];
 }
 
 // SAVE: training forward (inputs and hidden activations also go to HBM); a template parameter because the stores'
@@ -2232,6 +2279,41 @@ NAQS_API int naqs_net_create(const naqs_net_config_t *cfg, int device, naqs_net_
     return NAQS_OK;
 }
 
+NAQS_API int naqs_net_create_amp_layers(const naqs_net_config_t *cfg, int32_t n_amp_hidden, int device, naqs_net_t **out) {
+    if (!cfg || !out) return NAQS_ERR_INVALID;
+    *out = nullptr;
+    if (n_amp_hidden < 1 || n_amp_hidden > naqs::MAX_AMP_LAYERS) return NAQS_ERR_INVALID;
+    if (n_amp_hidden == 1) return naqs_net_create(cfg, device, out);
+    if (cfg->aggregate_phase != 0) return NAQS_ERR_UNSUPPORTED;           // (deep blocks: the single-phase family only)
+    if (cfg->amp_hidden > 0 && ((cfg->amp_hidden & 15) || cfg->amp_hidden > 128)) return NAQS_ERR_UNSUPPORTED;
+    naqs_net_t *net = nullptr;
+    int st = naqs_net_create(cfg, device, &net);
+    if (st != NAQS_OK) return st;
+    const NetDims &d = net->dims;
+    const int L = n_amp_hidden;
+    int64_t off = 0, doff = 0;
+    for (int n = 0; n < d.P; ++n) {                       // state_dict order, block by block
+        const int64_t f = naqs::deep_pair_floats(d.Ha, d.n_out_amp, L, n);
+        net->amp_src_off[n] = off;
+        net->deep_off[n] = doff;
+        off += f;
+        doff += (f + 3) & ~3ll;
+    }
+    const int64_t delta = off - net->amp_params;          // the phase layers follow the deeper blocks
+    for (int64_t &o : net->phase_src_off) o += delta;
+    net->amp_params = off;
+    net->n_params += delta;
+    net->amp_depth = L;
+    net->deep_floats = doff;
+    DeviceGuard guard;
+    st = guard.init(device);
+    if (st == NAQS_OK && net->d_wamp) { (void)hipFree(net->d_wamp); net->d_wamp = nullptr; }     // (the depth-1 fragments: never read)
+    if (st == NAQS_OK && hipMalloc((void **)&net->d_wdeep, (size_t)doff * sizeof(float)) != hipSuccess) st = NAQS_ERR_NOMEM;
+    if (st != NAQS_OK) { naqs_net_destroy(net); return st; }
+    *out = net;
+    return NAQS_OK;
+}
+
 NAQS_API int naqs_net_destroy(naqs_net_t *net) {
     if (!net) return NAQS_OK;
     DeviceGuard guard;
@@ -2242,6 +2324,7 @@ NAQS_API int naqs_net_destroy(naqs_net_t *net) {
     if (net->d_wph) (void)hipFree(net->d_wph);
     if (net->d_wh) (void)hipFree(net->d_wh);
     if (net->d_wamp) (void)hipFree(net->d_wamp);
+    if (net->d_wdeep) (void)hipFree(net->d_wdeep);
     if (net->d_wt) (void)hipFree(net->d_wt);
     if (net->d_scratch) (void)hipFree(net->d_scratch);
     if (net->d_samp) (void)hipFree(net->d_samp);
@@ -2282,6 +2365,16 @@ static size_t phase_slab_bytes(const NetDims &d, int fmt) { return (size_t)(fmt 
 static int phase_rb_max(const NetDims &d, int fmt) {
     if (fmt == 0) return 4;
     return (int)std::min<size_t>(fmt == 2 ? 4 : 3, (size_t)(155 * 1024) / phase_slab_bytes(d, fmt));
+}
+
+// deep amplitude blocks: their f32 copy (naqs_amp_deep.hpp) — what every deep kernel reads
+static int pack_deep(naqs_net *net, const float *flat_dev, hipStream_t s) {
+    const NetDims &d = net->dims;
+    const int64_t biggest = naqs::deep_pair_floats(d.Ha, d.n_out_amp, net->amp_depth, d.P - 1);
+    NAQS_KLAUNCH(deep_pack_kernel, dim3((unsigned)std::min<int64_t>(64, (biggest + 255) / 256), (unsigned)d.P), dim3(256), 0, s, flat_dev,
+                       naqs::deep_amp(net), d.Ha, d.n_out_amp, net->d_wdeep);
+    HIP_TRY(hipGetLastError());
+    return NAQS_OK;
 }
 
 static int pack_blocks(const NetDims &d, const int64_t *src_off, float *dst, const float *flat_dev, hipStream_t s) {
@@ -2335,7 +2428,9 @@ NAQS_API int naqs_net_set_amp_weights(naqs_net_t *net, const float *flat_dev, in
                                                 //  copy of it would write the blocks from the OTHER parameter vector over these)
     // rows AND fragments: the sampler picks the matrix-core form of the block MLPs whenever the fragments are current, and the
     // two forms round differently — the same (parameters, seed) must not draw differently depending on which call packed last
-    st = pack_amp_both(net, flat_dev, reinterpret_cast<hipStream_t>(stream));
+    // (deep blocks: their f32 copy is the only form)
+    st = net->amp_depth > 1 ? pack_deep(net, flat_dev, reinterpret_cast<hipStream_t>(stream))
+                            : pack_amp_both(net, flat_dev, reinterpret_cast<hipStream_t>(stream));
     if (st != NAQS_OK) return st;
     net->have_amp_weights = true;
     return NAQS_OK;
@@ -2375,6 +2470,10 @@ static int pack_single_phase(naqs_net *net, const float *flat_dev, hipStream_t s
     const int gy_amp = d.P + (net->d_wamp ? d.P : 0), gy_phase = d.n_lin + wb.n;
     naqs::PhaseRaw *raw = net->d_raw;
     if (mode == PACK_DEFER && (fmt != 2 || net->d_wamp == nullptr || net->amp_head_packed <= 0)) mode = PACK_AMP;      // (nothing to host the amplitude share with)
+    if (net->amp_depth > 1 && (mode == PACK_ALL || mode == PACK_AMP)) {      // (deep blocks: d_wamp is null, so no PACK_DEFER)
+        st = pack_deep(net, flat_dev, s);
+        if (st != NAQS_OK) return st;
+    }
     if (mode == PACK_ALL || mode == PACK_AMP || mode == PACK_DEFER) {
         net->packed_f32 = with_f32 != 0;
         net->packed_fmt = fmt;
@@ -2408,9 +2507,11 @@ static int pack_single_phase(naqs_net *net, const float *flat_dev, hipStream_t s
             net->have_wt = true;
         }
     } else if (mode == PACK_AMP) {
-        NAQS_KLAUNCH(pack_net_kernel, dim3(std::min(256, (amp_biggest + 255) / 256), gy_amp), dim3(256), 0, s, flat_dev, d, so, jobs, wb, net->d_w,
-                           net->d_wh, net->d_wamp, with_f32, fmt, raw, net->d_scales, 0, 0u, net->ctl);
-        HIP_TRY(hipGetLastError());
+        if (net->amp_depth == 1) {                         // (deep blocks: pack_deep above is their whole amplitude share)
+            NAQS_KLAUNCH(pack_net_kernel, dim3(std::min(256, (amp_biggest + 255) / 256), gy_amp), dim3(256), 0, s, flat_dev, d, so, jobs, wb,
+                               net->d_w, net->d_wh, net->d_wamp, with_f32, fmt, raw, net->d_scales, 0, 0u, net->ctl);
+            HIP_TRY(hipGetLastError());
+        }
         net->pack_pending = flat_dev;
         net->pack_pending_amp = false;
         net->pack_stream = s;
@@ -2575,6 +2676,21 @@ int naqs::net_amp_forward(naqs_net *net, int64_t M, const uint64_t *keys_dev, hi
     }
     if (!launch) return NAQS_OK;
     const ElocFeed none{};
+    if (net->amp_depth > 1) {
+        const int CT = d.Ha >> 4;
+        const int64_t items = (M + 15) / 16 * d.P;
+        const unsigned grid = (unsigned)((items + DEEPK_WAVES - 1) / DEEPK_WAVES);
+        const naqs::DeepAmp da = naqs::deep_amp(net);
+        std::snprintf(net->last_amp, sizeof(net->last_amp), "amp_deep_kernel<%d, L=%d>", CT, net->amp_depth);
+        switch (CT) {
+#define NAQS_DEEP(C) case C: NAQS_KLAUNCH(amp_deep_kernel<C>, dim3(grid), dim3(DEEPK_WAVES * 64), 0, s, d, net->d_wdeep, da, M, keys_dev, net->d_scratch, feed ? *feed : none); break;
+            NAQS_DEEP(1) NAQS_DEEP(2) NAQS_DEEP(3) NAQS_DEEP(4) NAQS_DEEP(5) NAQS_DEEP(6) NAQS_DEEP(7) NAQS_DEEP(8)
+#undef NAQS_DEEP
+            default: return NAQS_ERR_UNSUPPORTED;
+        }
+        HIP_TRY(hipGetLastError());
+        return NAQS_OK;
+    }
     if (net->d_wamp != nullptr && net->wamp_fresh && naqs::env_int("NAQS_AMP_MODE", 1) != 0) {      // matrix-core form (0: the VALU amp_kernel)
         const int64_t waves = (M + AMPK_TG * 16 - 1) / (AMPK_TG * 16) * d.P;
         const unsigned grid = (unsigned)((waves + AMPK_WAVES - 1) / AMPK_WAVES);
@@ -2912,7 +3028,8 @@ NAQS_API int naqs_net_prof_read(naqs_net_t *net, double *total_ms, int64_t *laun
 
 NAQS_API int naqs_net_last_kernel(const naqs_net_t *net, char *buf, int buf_len) {
     if (!net || !buf || buf_len <= 0) return NAQS_ERR_INVALID;
-    std::snprintf(buf, (size_t)buf_len, "%s", net->last_kernel);
+    if (net->amp_depth > 1 && net->last_deep[0] != 0) std::snprintf(buf, (size_t)buf_len, "%s; %s", net->last_kernel, net->last_deep);
+    else std::snprintf(buf, (size_t)buf_len, "%s", net->last_kernel);
     return NAQS_OK;
 }
 

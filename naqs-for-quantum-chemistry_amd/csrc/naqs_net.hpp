@@ -254,6 +254,13 @@ struct naqs_net {
     std::vector<int> phase_K, phase_N;
     // aggregate_phase: one phase block per pair, described as a second "amplitude-shaped" network (4 raw outputs, no
     // symmetry, the realised outcome's output is the pair's phase): the amplitude kernels run on it in raw mode
+    // amplitude blocks with more than one hidden layer (naqs_net_create_amp_layers; naqs_amp_deep.hpp): amp_src_off / amp_params
+    // follow their layout, the kernels read the f32 copy d_wdeep (pair n at deep_off[n]) and d_w's amplitude rows are unused
+    int amp_depth = 1;
+    float *d_wdeep = nullptr;
+    int64_t deep_off[naqs::MAXP] = {};
+    int64_t deep_floats = 0;
+    char last_deep[96] = {0};               // the deep launches of the last sampler / backward call (naqs_net_last_kernel)
     bool aggregate = false;
     naqs::NetDims dph{};
     int64_t ph_src_off[naqs::MAXP] = {};          // per pair: offset of its phase block in the flat source

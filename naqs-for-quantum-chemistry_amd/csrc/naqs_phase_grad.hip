@@ -995,7 +995,7 @@ static int train_backward_impl(naqs_net_t *net, int64_t M, const uint64_t *keys_
         HIP_TRY(hipGetLastError());
     }
     // NAQS_TRAIN_MEGA=0: every piece its own launch
-    const bool mega = H == 2 && d.Ha == 64 && !side && naqs::env_int("NAQS_TRAIN_MEGA", 1) == 1;
+    const bool mega = H == 2 && d.Ha == 64 && net->amp_depth == 1 && !side && naqs::env_int("NAQS_TRAIN_MEGA", 1) == 1;
     // naqs_vmc_run's steps: the phase MLP's half of what follows goes to the side stream (see the launch below)
     const bool defer = net->defer_phase && mega && adam != nullptr && seed_delta;
     hipStream_t sp = s;

@@ -30,6 +30,7 @@
 #include "naqs_common.hpp"
 #include "naqs_net.hpp"
 #include "naqs_amp_mfma.hpp"
+#include "naqs_amp_deep.hpp"
 #include "naqs_rng.hpp"
 #include "naqs_pack.hpp"
 
@@ -367,6 +368,58 @@ __global__ __launch_bounds__(SB) void sample_expand_kernel(const NetDims d, cons
         }
     }
     // survivors of this workgroup
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) survivors += __shfl_down(survivors, off, 64);
+    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = survivors;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t tot_s = 0;
+        for (int i = 0; i < SB / WAVE; ++i) tot_s += s_red[i];
+        b.wg_total[blockIdx.x] = tot_s;
+    }
+}
+
+// sample_expand_kernel for deep amplitude blocks (naqs_net_create_amp_layers): wave w evaluates its 16 prefixes (the quads
+// 16 w .. 16 w + 15) as one item of naqs_amp_deep.hpp, then every quad draws its children exactly as expand_quad does —
+// same Philox keying by (prefix, level), so a draw depends only on the prefix and the seed.  sample_scatter_kernel follows.
+template <int CT>
+__global__ __launch_bounds__(SB) void sample_expand_deep_kernel(const NetDims d, const float *__restrict__ wdeep, const naqs::DeepAmp da,
+                                                                const int n, const SampleBufs b, const int cur, const uint32_t k0,
+                                                                const uint32_t k1) {
+    static_assert(EXP_PARENTS * 4 == SB, "a quad per prefix");
+    __shared__ __attribute__((aligned(16))) float s_outs[SB / WAVE][128];
+    __shared__ uint32_t s_red[SB / WAVE];
+    const int64_t U = b.U[n];
+    if (b.U[MAXP + 1] != 0 || (int64_t)blockIdx.x * EXP_PARENTS >= U) return;          // workgroup-uniform
+    const int64_t u = (int64_t)blockIdx.x * EXP_PARENTS + (threadIdx.x >> 2);
+    const bool active = u < U;
+    const uint32_t ab = active ? b.ab[cur][u] : 0u;
+    const int64_t cnt = active ? b.cnt[cur][u] : 0;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float *outs = s_outs[wave];
+    const uint32_t ab16 = (uint32_t)__shfl((int)ab, 4 * (lane & 15), 64);
+    naqs::amp_deep_item<CT>(d, wdeep + da.off[n], da.L, n, ab16, lane, outs);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    float t[5];
+#pragma unroll
+    for (int c = 0; c < 5; ++c) t[c] = outs[(lane >> 2) * 8 + c];
+    float p[4];
+    bool phys[4];
+    probs_from_outputs(d, n, t, ab & 0xffffu, ab >> 16, p, phys);
+    int64_t out[4];
+    split_quad(n, ab, cnt, k0, k1, p, phys, out, nullptr);
+    uint32_t survivors = 0;
+    if (active && (threadIdx.x & 3) == 0) {
+        const float pr = b.prob[cur][u];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            b.child_cnt[u * 4 + c] = out[c];
+            b.child_prob[u * 4 + c] = pr * p[c];
+            survivors += out[c] > 0 ? 1u : 0u;
+        }
+    }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) survivors += __shfl_down(survivors, off, 64);
     if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = survivors;
@@ -979,7 +1032,9 @@ static int net_sample_enqueue(naqs_net_t *net, int64_t n_samples, uint64_t seed,
     // 0: per-level launches only, 1 (default): 4 levels / 256 threads, 2: 5 levels / 1024 threads — measured slower
     // (94 us against 38 + 18 for the fifth level on its own: sixteen latency-bound waves on one CU)
     const int head = naqs::env_int("NAQS_SAMPLE_HEAD", 1);
-    const bool use_head = head >= 1 && ((head >= 2 && d.P > 5 && cap >= 1024) || (d.P > 4 && cap >= 256));
+    // deep amplitude blocks (naqs_net_create_amp_layers): one expand + scatter pair per level (sample_expand_deep_kernel)
+    const bool deep = net->amp_depth > 1;
+    const bool use_head = !deep && head >= 1 && ((head >= 2 && d.P > 5 && cap >= 1024) || (d.P > 4 && cap >= 256));
     if (!(use_head && !(head >= 2 && d.P > 5 && cap >= 1024))) {
         // no launch of this call can host a pending amplitude re-pack (naqs_vmc_step leaves it to the four-level head launch
         // below): the amplitude jobs in order first — every level reads them
@@ -1013,7 +1068,7 @@ static int net_sample_enqueue(naqs_net_t *net, int64_t n_samples, uint64_t seed,
     }
     // one launch per level (expand + compaction with a look-back scan across workgroups) unless NAQS_SAMPLE_FUSED=0 or
     // the level could need more workgroups than are resident at once (the look-back waits on lower-indexed workgroups)
-    const bool fused_levels = naqs::env_int("NAQS_SAMPLE_FUSED", 1) == 1;
+    const bool fused_levels = !deep && naqs::env_int("NAQS_SAMPLE_FUSED", 1) == 1;
     const int64_t resident_wg = (int64_t)net->cu_count * 8;
     if (net->samp_seq >= 0x00FFFFFFu) {                    // the 24-bit call tag is about to repeat: forget every old word
         HIP_TRY(hipMemsetAsync(b.wg_state, 0, (size_t)nws_cap * sizeof(unsigned long long), s));
@@ -1082,7 +1137,17 @@ static int net_sample_enqueue(naqs_net_t *net, int64_t n_samples, uint64_t seed,
                                keys_dev, counts_dev, probs_dev, clk_dev, wamp, early, seq);
             HIP_TRY(hipGetLastError());
         } else {
-            NAQS_KLAUNCH(sample_expand_kernel, dim3(grid_e), dim3(SB), lds, s, d, net->d_w, n, b, half, k0, k1, wamp);
+            if (deep) {
+                const naqs::DeepAmp da = naqs::deep_amp(net);
+                switch (d.Ha >> 4) {
+#define NAQS_DEEP(C) case C: NAQS_KLAUNCH(sample_expand_deep_kernel<C>, dim3(grid_e), dim3(SB), 0, s, d, net->d_wdeep, da, n, b, half, k0, k1); break;
+                    NAQS_DEEP(1) NAQS_DEEP(2) NAQS_DEEP(3) NAQS_DEEP(4) NAQS_DEEP(5) NAQS_DEEP(6) NAQS_DEEP(7) NAQS_DEEP(8)
+#undef NAQS_DEEP
+                    default: return NAQS_ERR_UNSUPPORTED;
+                }
+            } else {
+                NAQS_KLAUNCH(sample_expand_kernel, dim3(grid_e), dim3(SB), lds, s, d, net->d_w, n, b, half, k0, k1, wamp);
+            }
             HIP_TRY(hipGetLastError());
             NAQS_KLAUNCH(sample_scatter_kernel, dim3(grid), dim3(SB), 0, s, d, n, b, half, cap, last, keys_dev, counts_dev,
                                probs_dev);
@@ -1092,6 +1157,8 @@ static int net_sample_enqueue(naqs_net_t *net, int64_t n_samples, uint64_t seed,
         ++n;
         half ^= 1;
     }
+    if (deep) std::snprintf(net->last_deep, sizeof(net->last_deep), "sampler: %d x (sample_expand_deep_kernel<%d> + sample_scatter_kernel)",
+                            d.P, d.Ha >> 4);
     naqs::SampleFinishJob fin;
     fin.U = b.U; fin.P = d.P; fin.info = info_dev; fin.counts = counts_dev; fin.weights = weights_dev; fin.early = early; fin.seq = seq;
     fin.levels_out = net->d_info_alias + 4;

@@ -3,7 +3,8 @@
 The product path of the metric's "log-psi eval": two kernels instead of ~200 eager launches.
 Supported architecture families:
   * what the reference's published runs use (batch_train.sh:14): one hidden layer per amplitude block (a multiple of 16,
-    <= 128 units), a single phase block (``aggregate_phase=False``) of 1..8 hidden layers <= 512 wide;
+    <= 128 units), a single phase block (``aggregate_phase=False``) of 1..8 hidden layers <= 512 wide; with this single phase
+    block the amplitude blocks may also have 2..4 hidden layers of one width (``-n_layer``; ``naqs_net_create_amp_layers``);
   * the reference's default ansatz (experiments/run.py:11-31): the same amplitude blocks and one phase block per orbital
     pair (``aggregate_phase=True``), each with one hidden layer (multiple of 16, <= 128 units);
 both with or without the phase spin symmetry (``-phase_sym``, nade.py:281, 507-533, 590-610: spin-ordered inputs of the phase
@@ -69,7 +70,12 @@ class FusedLogPsi:
                                       "PyTorch modules")
         if len(m.phase_layers) != (m.P if self.aggregate else 1):
             raise NotImplementedError("fused log-psi: unexpected number of phase blocks")
-        if len(m.amp_layers[0].linears()) != 2:
+        amp_lin = m.amp_layers[0].linears()
+        # 1 hidden layer; or 2..4 of one width with a single phase block (naqs_net_create_amp_layers)
+        self.amp_depth = len(amp_lin) - 1
+        deep_ok = (not self.aggregate and 2 <= self.amp_depth <= _lib.NET_MAX_AMP_LAYERS
+                   and len({lin.out_features for lin in amp_lin[:-1]}) == 1)
+        if self.amp_depth != 1 and not deep_ok:
             raise NotImplementedError("fused log-psi: amplitude blocks need exactly one hidden layer")
         ha = m.amp_layers[0].linears()[0].out_features
         if ha % 16 or ha > 128:
@@ -102,8 +108,12 @@ class FusedLogPsi:
         cfg.aggregate_phase = int(self.aggregate)
         cfg.use_phase_spin_sym = int(self.phase_sym)          # -phase_sym with one phase block (nade.py:281, 507-533, 590-610)
         self._h = ctypes.c_void_p(None)
-        st = self._lib.naqs_net_create(ctypes.byref(cfg), self.device.index or 0, ctypes.byref(self._h))
-        _lib.check(st, "naqs_net_create")
+        if self.amp_depth == 1:
+            st = self._lib.naqs_net_create(ctypes.byref(cfg), self.device.index or 0, ctypes.byref(self._h))
+            _lib.check(st, "naqs_net_create")
+        else:
+            st = self._lib.naqs_net_create_amp_layers(ctypes.byref(cfg), self.amp_depth, self.device.index or 0, ctypes.byref(self._h))
+            _lib.check(st, "naqs_net_create_amp_layers")
         n = ctypes.c_int64(0)
         _lib.check(self._lib.naqs_net_param_count(self._h, ctypes.byref(n)), "naqs_net_param_count")
         self.n_params = n.value
