@@ -12,7 +12,11 @@ on the CPU is an exact-arithmetic stand-in for what the HIP backward computes in
                                the float32 arithmetic vmc_grad_kernel documents (naqs_grad.hip);
 * ``kink_free``                g with the rows near a kink zeroed;
 * ``log_psi_f64``              the forward alone, in chunks of rows (no graph): float64 numpy [M, 2];
-* ``sorted_rows``              the first m rows of a key set in the library's (ascending) order, with their reference rows.
+* ``sorted_rows``              the first m rows of a key set in the library's (ascending) order, with their reference rows;
+* ``log_amp_f64``              log|psi| alone, from the amplitude blocks' conditionals (no phase MLP): the sampler's target;
+* ``conditionals_f64``         one block's four conditional probabilities for a set of prefixes (the sampler's tree nodes);
+* ``SECTORS`` / ``sector_net`` one electron sector per orbital-pair count P = 2..16 and a default-initialised network on it;
+* ``random_keys``              distinct random physical keys of any sector.
 """
 import contextlib
 
@@ -151,3 +155,98 @@ def sorted_rows(keys, m, *tables):
     library's tables are kept in —, then each table's rows in that order)."""
     order = np.argsort(keys[:m], kind="stable")
     return (keys[:m][order],) + tuple(t[:m][order] for t in tables)
+
+
+def _model_order(wf, states):
+    """[M, N] (+-1, qubit order) -> (alpha, beta) occupations [M, P] (+-1) per model pair, in the network's dtype."""
+    dt = next(wf.model.parameters()).dtype
+    x = torch.as_tensor(states)[..., wf._q2m.cpu()].to(dt)
+    return x[:, 0::2], x[:, 1::2]
+
+
+def conditionals_f64(wf, states, n):
+    """Block n's conditionals for the prefixes of ``states`` ([U, N] +-1, qubit order; only model pairs 0..n-1 are read):
+    -> (p float64 [U, 4] = exp(2 log-amplitude) per outcome (a, b) -> a + 2 b, physical mask bool [U, 4]).  With the
+    softmax masked (FULL, or PARTIAL before the last pair) p sums to one over the physical outcomes and is 0 elsewhere."""
+    a, b = _model_order(wf, states)
+    with torch.no_grad():
+        la, phys = wf.model._block_log_amp(n, a[:, :n], b[:, :n])
+    return torch.exp(2 * la).double().numpy(), phys.numpy()
+
+
+def log_amp_f64(wf, states, chunk=1 << 16):
+    """log|psi| [M] of ``states`` ([M, N] +-1, qubit order) as the sum over pairs of the chosen outcome's conditional
+    log-amplitude (OrbitalNADE._block_log_amp, the sampler's formulation): log_psi_f64(...)[:, 0] without the phase MLP."""
+    states = torch.as_tensor(states)
+    out = np.empty(states.shape[0], np.float64)
+    with torch.no_grad():
+        for lo in range(0, states.shape[0], chunk):
+            a, b = _model_order(wf, states[lo:lo + chunk])
+            occ = ((a > 0).long() + 2 * (b > 0).long())
+            acc = torch.zeros(a.shape[0], dtype=torch.float64)
+            for n in range(wf.model.P):
+                la, _ = wf.model._block_log_amp(n, a[:, :n], b[:, :n])
+                acc += la.gather(1, occ[:, n:n + 1]).squeeze(1).double()
+            out[lo:lo + chunk] = acc.numpy()
+    return out
+
+
+# One sector per orbital-pair count P = 2..16: (name, qubits, n_alpha, n_beta, molecule of packing_terms.npz or None for a
+# synthetic sector).  P = 10 adds the extreme fillings: 1 of 10 alpha orbitals (H2_cc-pvdz), 9 of 10 (F2), 9 / 7 (O2).
+SECTORS = [
+    ("H2", 4, 1, 1, "H2"),
+    ("syn6_2_1", 6, 2, 1, None),              # synthetic, open shell
+    ("H2_6-31G", 8, 1, 1, "H2_6-31G"),
+    ("syn10_3_2", 10, 3, 2, None),            # synthetic: the one level after the sampler's head
+    ("LiH", 12, 2, 2, "LiH"),
+    ("BeH2", 14, 3, 3, "BeH2"),
+    ("NH3", 16, 5, 5, "NH3"),
+    ("CH4", 18, 5, 5, "CH4"),
+    ("LiF", 20, 6, 6, "LiF"),
+    ("H2_cc-pvdz", 20, 1, 1, "H2_cc-pvdz"),
+    ("F2", 20, 9, 9, "F2"),
+    ("O2", 20, 9, 7, "O2"),
+    ("H2S", 22, 9, 9, "H2S"),
+    ("PH3", 24, 9, 9, "PH3"),
+    ("H2O_6-31G", 26, 5, 5, "H2O_6-31G"),
+    ("LiCl", 28, 10, 10, "LiCl"),
+    ("Li2O", 30, 7, 7, "Li2O"),
+    ("syn32_8_8", 32, 8, 8, None),            # synthetic: the ABI's 16 pairs, 32-bit keys
+]
+
+
+def sector(name):
+    return next(r for r in SECTORS if r[0] == name)
+
+
+def sector_net(name, device="cuda", seed=0, masking="PARTIAL", aggregate=False, phase_sym=False, amp_layers=1, amp_hidden=64,
+               phase_hidden=(512, 512)):
+    """(hilbert, network) on sector ``name``: default-initialised from ``seed``; by default the published shape (amplitude
+    width 64, one phase MLP [512, 512], amplitude spin symmetry, PARTIAL masking).  ``aggregate``: one phase block of
+    ``phase_hidden`` per pair (run.py's default ansatz); ``amp_layers``: hidden layers per amplitude block."""
+    from naqs_amd.hilbert import Encoding, Hilbert
+    from naqs_amd.nade import NadeMasking
+    from naqs_amd.wavefunction import NAQSComplex_NADE_orbitals
+    _, N, na, nb, _ = sector(name)
+    hil = Hilbert.get(N, na, nb, encoding=Encoding.SIGNED)
+    torch.manual_seed(seed)
+    wf = NAQSComplex_NADE_orbitals(hil, device=device, qubit_ordering=-1, masking=NadeMasking[masking],
+                                   amp_hidden_size=[amp_hidden] * amp_layers, phase_hidden_size=list(phase_hidden),
+                                   use_amp_spin_sym=True, use_phase_spin_sym=phase_sym, aggregate_phase=aggregate,
+                                   n_alpha_electrons=na, n_beta_electrons=nb)
+    return hil, wf
+
+
+def random_keys(hil, M, seed):
+    """M distinct physical keys of ``hil``'s sector (even qubits alpha, odd beta), in random order; M <= hil.size."""
+    assert M <= hil.size, (M, hil.size)
+    rs = np.random.RandomState(seed)
+    N, na, nb = hil.N, hil.N_alpha, hil.N_beta
+    keys = np.zeros(0, np.uint64)
+    while len(keys) < M:
+        a = np.argsort(rs.random_sample((2 * M, N // 2)), 1)
+        ka = (np.uint64(1) << (2 * a[:, :na]).astype(np.uint64)).sum(1, dtype=np.uint64)
+        b = np.argsort(rs.random_sample((2 * M, N // 2)), 1)
+        kb = (np.uint64(1) << (2 * b[:, :nb] + 1).astype(np.uint64)).sum(1, dtype=np.uint64)
+        keys = np.unique(np.concatenate([keys, ka | kb]))
+    return rs.permutation(keys)[:M]

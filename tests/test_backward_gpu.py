@@ -210,17 +210,8 @@ def _random_net(phase_hidden):
 
 
 def _random_keys(hil, M, seed):
-    """M distinct physical keys of a 30-qubit space (even qubits alpha, odd beta), in random order."""
-    rs = np.random.RandomState(seed)
-    N, na, nb = hil.N, 7, 7
-    keys = np.zeros(0, np.uint64)
-    while len(keys) < M:
-        a = np.argsort(rs.random_sample((2 * M, N // 2)), 1)
-        ka = (np.uint64(1) << (2 * a[:, :na]).astype(np.uint64)).sum(1, dtype=np.uint64)
-        b = np.argsort(rs.random_sample((2 * M, N // 2)), 1)
-        kb = (np.uint64(1) << (2 * b[:, :nb] + 1).astype(np.uint64)).sum(1, dtype=np.uint64)
-        keys = np.unique(np.concatenate([keys, ka | kb]))
-    return rs.permutation(keys)[:M]
+    """M distinct physical keys of the sector (the 30-qubit 7 + 7 space here), in random order."""
+    return gr.random_keys(hil, M, seed)
 
 
 def _whole_space(hil, seed):

@@ -134,3 +134,79 @@ def test_sampler_probs_are_psi_squared_in_float64(fix):
     assert probs.dtype == torch.float64 and len(probs) > 200 and counts.sum() > 0
     want = np.exp(2 * gr.log_psi_f64(wf, states)[:, 0])
     assert np.max(np.abs(probs.numpy() / want - 1)) < 1e-13
+
+
+# ------------------------------------------------------------------------------- the orbital-pair sectors (test_pairs_gpu.py)
+def test_sector_table_matches_the_packed_molecules():
+    """One sector per P = 2..16 (P = 10 four times: the extreme fillings); a molecule's row is its qubit count and the
+    electron split system.Molecule gives packing_terms.npz's electrons and multiplicity (as test_packing.py packs them)."""
+    import math
+    from naqs_amd import system
+    z = np.load(os.path.join(GOLDEN, "packing_terms.npz"))
+    assert sorted({r[1] // 2 for r in gr.SECTORS}) == list(range(2, 17))
+    assert sorted(r[1] for r in gr.SECTORS if r[1] == 20) == [20] * 4
+    for name, N, na, nb, mol in gr.SECTORS:
+        assert N % 2 == 0 and 1 <= na <= N // 2 and 1 <= nb <= N // 2, name
+        if mol is None:
+            continue
+        m = object.__new__(system.Molecule)
+        m.n_electrons, m.multiplicity = (int(v) for v in z[f"{mol}:electrons"])
+        assert (z[f"{mol}:ops"].shape[1], m.get_n_alpha_electrons(), m.get_n_beta_electrons()) == (N, na, nb), name
+    sizes = {name: math.comb(N // 2, na) * math.comb(N // 2, nb) for name, N, na, nb, _ in gr.SECTORS}
+    assert (sizes["H2"], sizes["syn6_2_1"], sizes["H2_6-31G"], sizes["syn10_3_2"], sizes["H2_cc-pvdz"], sizes["F2"],
+            sizes["O2"], sizes["H2O_6-31G"], sizes["LiCl"]) == (4, 9, 16, 100, 100, 100, 1200, 1656369, 1002001)
+
+
+def test_random_keys_of_any_sector():
+    from naqs_amd.hilbert import Hilbert
+    for N, na, nb, M in ((4, 1, 1, 4), (6, 2, 1, 9), (20, 9, 7, 500), (32, 8, 8, 2000)):
+        hil = Hilbert.get(N, na, nb)
+        k = gr.random_keys(hil, M, 3)
+        assert len(k) == M and len(np.unique(k)) == M and hil.is_physical(k).all()
+        assert np.array_equal(k, gr.random_keys(hil, M, 3))
+    assert (gr.random_keys(Hilbert.get(32, 8, 8), 2000, 3) >> np.uint64(31)).any()        # (bit 31: beta orbital 15)
+
+
+@pytest.mark.parametrize("fix", ["LiH", "H2O", "LiH_fullmask", "LiH_noampsym"])
+def test_log_amp_is_log_psi_without_the_phase(fix):
+    """log_amp_f64 (the sampler's per-block conditionals) equals log_psi_f64[:, 0] (the teacher-forced forward) on the whole
+    space — and -inf where the forward has -inf (FULL masking, unphysical keys)."""
+    from naqs_amd.hilbert import Hilbert
+    hil, wf = gr.f64_copy(fix)
+    keys = np.sort(hil._all_keys()).astype(np.uint64)
+    if fix.endswith("fullmask"):
+        full = Hilbert.get(hil.N, hil.N_alpha, hil.N_beta)
+        extra = np.setdiff1d(np.arange(1 << hil.N, dtype=np.uint64)[::7], keys)[:300]
+        assert not full.is_physical(extra).any()
+        keys = np.concatenate([keys, extra])
+    s = hil.idx2state(torch.as_tensor(keys.astype(np.int64)))
+    a = gr.log_amp_f64(wf, s, chunk=97)
+    b = gr.log_psi_f64(wf, s)[:, 0]
+    assert np.array_equal(np.isfinite(a), np.isfinite(b))
+    if fix.endswith("fullmask"):
+        assert (~np.isfinite(a)).sum() >= 250
+    f = np.isfinite(b)
+    assert np.max(np.abs(a[f] - b[f])) < 1e-12
+
+
+@pytest.mark.parametrize("masking", ["PARTIAL", "FULL"])
+def test_conditionals_multiply_to_psi_squared(masking):
+    """LiH: the product of conditionals_f64 along each key's path is exp(2 log|psi|); under masking the conditionals of
+    every node sum to one over the physical outcomes, which alone carry mass (PARTIAL: except the last pair)."""
+    from naqs_amd.nade import NadeMasking
+    from test_nade import make_wf
+    hil, wf = make_wf("LiH", golden("nade_LiH.npz"), masking=NadeMasking[masking])
+    _, wf = gr.f64_copy(wf)
+    keys = np.sort(hil._all_keys())
+    s = hil.idx2state(torch.as_tensor(keys))
+    ms = s[:, wf._q2m]
+    occ = ((ms[:, 0::2] > 0).long() + 2 * (ms[:, 1::2] > 0).long()).numpy()
+    prod = np.ones(len(keys))
+    for n in range(wf.model.P):
+        p, phys = gr.conditionals_f64(wf, s, n)
+        assert p.shape == (len(keys), 4) and phys.shape == (len(keys), 4)
+        if masking == "FULL" or n < wf.model.P - 1:
+            assert np.all(p[~phys] == 0) and np.allclose(p.sum(1), 1, rtol=0, atol=1e-14)
+        prod *= p[np.arange(len(keys)), occ[:, n]]
+    want = np.exp(2 * gr.log_psi_f64(wf, s)[:, 0])
+    assert np.max(np.abs(prod / want - 1)) < 1e-12
