@@ -198,8 +198,9 @@ int naqs_prof_stride(naqs_ham_t *h, int stride);
  * _forward_predict (src/naqs/network/nade.py:738-770) for the published architecture family:
  * one amplitude MLP per orbital pair (one hidden layer; 2..4 of one width through naqs_net_create_amp_layers), and either
  * a single phase MLP on the last pair (aggregate_phase = False: -single_phase, the published runs) or one single-hidden-layer
- * phase block per pair whose outputs are summed (aggregate_phase = True: the reference's default); SoftmaxLogProbAmps
- * amplitudes, no phase symmetry.
+ * phase block per pair whose outputs are summed (aggregate_phase = True: the reference's default), or no phase MLP and the
+ * last amplitude block's output layer carrying the phase rows (naqs_net_create_combined: -single_phase -comb_amp_phase);
+ * SoftmaxLogProbAmps amplitudes, with or without the phase spin symmetry.
  * ============================================================================================== */
 typedef struct naqs_net naqs_net_t;
 
@@ -236,6 +237,18 @@ int naqs_net_create(const naqs_net_config_t *cfg, int device, naqs_net_t **out);
  * launch in front of the phase kernel, one expand + scatter launch pair per sampler level, their own backward launch), so
  * naqs_vmc_step / naqs_vmc_run take the non-speculative order for them. */
 int naqs_net_create_amp_layers(const naqs_net_config_t *cfg, int32_t n_amp_hidden, int device, naqs_net_t **out);
+/* naqs_net_create for combined amplitude-phase blocks with a single phase (the reference's -single_phase -comb_amp_phase,
+ * nade.py:294-303, 555-560): no phase MLP; every block is Linear(max(1, 2n), amp_hidden) + ReLU + Linear(amp_hidden, n_out), and
+ * the last block's output layer has n_out_amp + n_out_phase rows — 5 + 3 with use_amp_spin_sym (spin-ordered inputs, the phase
+ * row [0, 1, 1, 2][occ], + pi (N_01 mod 2)), 4 + 4 without; rows n_out_amp.. give the phase, earlier blocks contribute none.
+ * NAQS_ERR_UNSUPPORTED: aggregate_phase = 1, or an amp_hidden that is not a multiple of 16 <= 128; NAQS_ERR_INVALID:
+ * use_phase_spin_sym != use_amp_spin_sym (the reference forces them equal).  n_phase_hidden and phase_hidden are ignored.
+ * The flat layout is the state_dict order, block by block; the last block is W1 [Ha][2(P-1)], b1 [Ha],
+ * W2 [n_out_amp + n_out_phase][Ha], b2 [n_out_amp + n_out_phase].  naqs_net_param_count and naqs_net_amp_param_count both count
+ * every parameter; naqs_net_set_amp_weights packs them all.  The sampler draws exactly what a naqs_net_create handle with the same
+ * amplitude rows draws; naqs_net_amp_backward differentiates log|psi| only (zero gradient for the phase rows); naqs_vmc_step /
+ * naqs_vmc_run take the non-speculative order; the naqs_vmc_shard_* calls return NAQS_ERR_UNSUPPORTED. */
+int naqs_net_create_combined(const naqs_net_config_t *cfg, int device, naqs_net_t **out);
 int naqs_net_destroy(naqs_net_t *net);
 /* Number of float parameters expected by naqs_net_set_weights: the reference's state_dict order,
  * flattened (amp_layers.0.layers.0.0.weight, .bias, amp_layers.0.layers.1.0.weight, .bias, ...,
@@ -284,7 +297,8 @@ int naqs_net_spec_counts(const naqs_net_t *net, int64_t counts[2]);
  * The samples do not depend on the switch. */
 int naqs_net_share_device(naqs_net_t *net, int on, int64_t *turns);
 /* Name of the log-psi kernel the most recent naqs_net_logpsi / naqs_logpsi_eloc / training forward launched, followed by
- * " + <kernel>" for the amplitude launch in front of it (or the aggregate-phase launches).  Handles of
+ * " + <kernel>" for the amplitude launch in front of it (or the aggregate-phase launches, or the combined blocks' phase head and
+ * sums: " + comb_head_kernel + comb_finish_kernel").  Handles of
  * naqs_net_create_amp_layers append "; sampler: ..." or "; backward: ..." for the deep launches of the most recent sampler or
  * amplitude-backward call. */
 int naqs_net_last_kernel(const naqs_net_t *net, char *buf, int buf_len);

@@ -89,6 +89,41 @@ __global__ __launch_bounds__(512) void amp_backward2_kernel(const NetDims d0, co
                                    (int)blockIdx.x, (int)gridDim.x, g_stride);
 }
 
+// combined amplitude-phase blocks (naqs_net_create_combined): the amplitude blocks (blockIdx.y < P, on g[:, 0]) and the phase head
+// (blockIdx.y == P: pair P - 1 of d1, raw, on g[:, 1]) in ONE launch; per workgroup the partial sums of both in the layout of
+// net->d_cflat (amplitude blocks in the plain layout, the head at head_off)
+__global__ __launch_bounds__(512) void comb_backward_kernel(const NetDims d0, const float *__restrict__ w0, const AmpSrc src0,
+                                                            const NetDims d1, const float *__restrict__ w1, const int64_t head_off,
+                                                            const int64_t M, const uint64_t *__restrict__ keys, const float *__restrict__ g,
+                                                            const int g_stride, float *__restrict__ partial, const int64_t partial_stride) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int n = blockIdx.y;
+    float *out = partial + (int64_t)blockIdx.x * partial_stride;
+    if (n < d0.P)
+        naqs::ampbw::pair_dispatch(n, d0, w0, M, keys, g, out + src0.off[n], smem, 0, (int)blockIdx.x, (int)gridDim.x, g_stride);
+    else
+        naqs::ampbw::pair_dispatch(d1.P - 1, d1, w1, M, keys, g + 1, out + head_off, smem, 1, (int)blockIdx.x, (int)gridDim.x, g_stride);
+}
+
+// ... and the gradient in the flat layout: element e sums its amplitude partials, then (with_head) its head partials, each over the
+// workgroups in order, and adds the two (the last block's W1 / b1 have both; naqs::comb_src); with a.p also Adam's update of e
+__global__ __launch_bounds__(256) void comb_grad_finish_kernel(const naqs::CombLayout c, const int n_partials, const int64_t partial_stride,
+                                                               const float *__restrict__ partial, const int with_head,
+                                                               float *__restrict__ grad, const naqs::AdamArgs a) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= c.total) return;
+    int64_t pa, ph;
+    naqs::comb_src(c, e, pa, ph);
+    float ga = 0.0f, gh = 0.0f;
+    if (pa >= 0)
+        for (int b = 0; b < n_partials; ++b) ga += partial[(int64_t)b * partial_stride + pa];
+    if (ph >= 0 && with_head)
+        for (int b = 0; b < n_partials; ++b) gh += partial[(int64_t)b * partial_stride + c.amp + ph];
+    const float gi = pa >= 0 && ph >= 0 && with_head ? ga + gh : (pa >= 0 ? ga : gh);
+    grad[e] = gi;
+    if (a.p != nullptr) naqs::adam_update(a, e, gi);
+}
+
 __global__ __launch_bounds__(256) void amp_reduce_kernel(int64_t count, int n_partials, int64_t partial_stride,
                                                          const float *__restrict__ partial, float *__restrict__ out) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -348,6 +383,36 @@ int naqs::net_blocks_backward2(naqs_net *net, int64_t M, const uint64_t *keys_de
     return NAQS_OK;
 }
 
+int naqs::net_comb_backward(naqs_net *net, int64_t M, const uint64_t *keys_dev, const float *g_dev, int g_stride, bool with_head,
+                             float *grad_dev, const naqs::AdamArgs *adam, hipStream_t s) {
+    const NetDims &d0 = net->dims, &d1 = net->dph;
+    if (!net->comb || d0.Ha > 128 || (d0.Ha & 15) || d1.Ha != d0.Ha || d1.P != d0.P) return NAQS_ERR_UNSUPPORTED;
+    if (M <= 0) {
+        if (adam) return NAQS_ERR_INVALID;
+        HIP_TRY(hipMemsetAsync(grad_dev, 0, (size_t)net->n_params * sizeof(float), s));
+        return NAQS_OK;
+    }
+    const int n_wg = (int)std::min<int64_t>(MAX_TILE_WGS, (M + GT - 1) / GT);
+    const int64_t stride = (net->comb_amp + net->comb_head + 3) & ~3ll;
+    if (!net->d_cpart) HIP_TRY(hipMalloc((void **)&net->d_cpart, (size_t)MAX_TILE_WGS * stride * sizeof(float)));
+    const size_t lds = std::max(naqs::ampbw::smem_floats(d0), naqs::ampbw::smem_floats(d1)) * sizeof(float);
+    if (lds > 156 * 1024) return NAQS_ERR_UNSUPPORTED;
+    if (!net->comb_attr_set) {
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&comb_backward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
+        net->comb_attr_set = true;
+    }
+    AmpSrc src;
+    for (int n = 0; n < MAXP; ++n) src.off[n] = net->amp_src_off[n] - net->amp_src_off[0];
+    NAQS_KLAUNCH(comb_backward_kernel, dim3((unsigned)n_wg, (unsigned)(d0.P + (with_head ? 1 : 0))), dim3((unsigned)((d0.Ha >> 4) * WAVE)), lds, s,
+                       d0, net->d_w, src, d1, net->d_wph, net->comb_amp, M, keys_dev, g_dev, g_stride, net->d_cpart, stride);
+    HIP_TRY(hipGetLastError());
+    const naqs::CombLayout c = naqs::comb_layout(net);
+    NAQS_KLAUNCH(comb_grad_finish_kernel, dim3((unsigned)((c.total + 255) / 256)), dim3(256), 0, s, c, n_wg, stride, net->d_cpart,
+                       with_head ? 1 : 0, grad_dev, adam ? *adam : naqs::AdamArgs{});
+    HIP_TRY(hipGetLastError());
+    return NAQS_OK;
+}
+
 NAQS_API int naqs_net_amp_backward(naqs_net_t *net, int64_t M, const uint64_t *keys_dev, const float *g_dev,
                                    float *grad_dev, void *stream) {
     if (!net || M < 0 || !grad_dev || (M > 0 && (!keys_dev || !g_dev))) return NAQS_ERR_INVALID;
@@ -357,6 +422,8 @@ NAQS_API int naqs_net_amp_backward(naqs_net_t *net, int64_t M, const uint64_t *k
     if (st != NAQS_OK) return st;
     st = naqs::net_flush_amp_pack(net, reinterpret_cast<hipStream_t>(stream));
     if (st != NAQS_OK) return st;
+    // combined blocks: log|psi| only — the phase rows get zero gradient, the flat layout is the whole parameter vector's
+    if (net->comb) return naqs::net_comb_backward(net, M, keys_dev, g_dev, 1, false, grad_dev, nullptr, reinterpret_cast<hipStream_t>(stream));
     return naqs::net_blocks_backward(net, net->dims, net->d_w, net->amp_src_off, net->amp_params, M, keys_dev, g_dev, grad_dev, 0,
                                      reinterpret_cast<hipStream_t>(stream));
 }

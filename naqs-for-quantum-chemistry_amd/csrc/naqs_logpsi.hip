@@ -172,6 +172,33 @@ __global__ __launch_bounds__(256) void agg_finish_kernel(const int P, const int6
     if (feed.psi != nullptr) naqs::feed_psi(feed, i, la, ph);
 }
 
+// combined amplitude-phase blocks (naqs_net_create_combined): the phase head — the last block's hidden layer and phase rows, a raw
+// block of pair P - 1 (d = net->dph) — through amp_body, which writes row P - 1 of `scratch`.  The launch has amp_kernel's shape;
+// the workgroups of the other pairs leave at once.
+__global__ __launch_bounds__(AMP_TILES * AMP_SPLIT * WAVE) void comb_head_kernel(const NetDims d, const float *__restrict__ w,
+                                                                                 int64_t M, const uint64_t *__restrict__ keys,
+                                                                                 float *__restrict__ scratch) {
+    __shared__ float s_part[AMP_TILES][AMP_SPLIT][5][WAVE];
+    extern __shared__ __attribute__((aligned(16))) float s_w[];
+    if ((int)blockIdx.y != d.P - 1) return;              // workgroup-uniform, before any barrier
+    const ElocFeed none{};
+    amp_body(d, w, M, keys, scratch, none, 1, s_part, s_w);
+}
+
+// combined blocks' epilogue: (log|psi|, phase) = (sum_n conditional log-amplitudes, pair 0 first, the head's phase); on the fused
+// log-psi + E_loc entry also psi in float64
+__global__ __launch_bounds__(256) void comb_finish_kernel(const int P, const int64_t M, const float *__restrict__ s_amp,
+                                                          const float *__restrict__ s_head, float2 *__restrict__ out,
+                                                          const ElocFeed feed) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= M) return;
+    float la = 0.0f;
+    for (int n = 0; n < P; ++n) la += s_amp[(int64_t)n * M + i];
+    const float ph = s_head[i];
+    out[i] = make_float2(la, ph);
+    if (feed.psi != nullptr) naqs::feed_psi(feed, i, la, ph);
+}
+
 // ------------------------------------------------------------------------------------------------
 // phase MLP on the f32 matrix cores
 // ------------------------------------------------------------------------------------------------
@@ -2020,6 +2047,27 @@ __global__ __launch_bounds__(256) void pack_amp2_kernel(const float *__restrict_
     else pack_amp_mfma_body(flat, d0, so0, wamp, blockIdx.y, (int)blockIdx.x, (int)gridDim.x);
 }
 
+// combined blocks: the flat parameters -> [amplitude blocks in the plain layout | phase head] (naqs::comb_src)
+__global__ __launch_bounds__(256) void comb_split_kernel(const float *__restrict__ flat, const naqs::CombLayout c, float *__restrict__ dst) {
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < c.total; e += (int64_t)gridDim.x * 256) {
+        int64_t pa, ph;
+        naqs::comb_src(c, e, pa, ph);
+        const float v = flat[e];
+        if (pa >= 0) dst[pa] = v;
+        if (ph >= 0) dst[c.amp + ph] = v;
+    }
+}
+// ... and that copy into the kernels' layouts in one launch: blockIdx.y < P the amplitude rows, < 2 P their fragments (when they
+// exist) — what pack_amp_both_kernel writes for a plain handle — and 2 P the head's rows (pair P - 1 of d1, from so1)
+__global__ __launch_bounds__(256) void comb_pack_kernel(const float *__restrict__ src, const NetDims d0, const AmpSrcOff so0,
+                                                        float *__restrict__ w0, ushort_t *__restrict__ wamp, const NetDims d1,
+                                                        const AmpSrcOff so1, float *__restrict__ w1) {
+    const int y = blockIdx.y;
+    if (y < d0.P) pack_amp_body(src, d0, so0, w0, y, (int)blockIdx.x, (int)gridDim.x);
+    else if (y < 2 * d0.P) { if (wamp != nullptr) pack_amp_mfma_body(src, d0, so0, wamp, y - d0.P, (int)blockIdx.x, (int)gridDim.x); }
+    else pack_amp_body(src, d1, so1, w1, d1.P - 1, (int)blockIdx.x, (int)gridDim.x);
+}
+
 __device__ __forceinline__ void pack_phase_f32(const float *__restrict__ src, int K, int N, int K_pad, int N_pad,
                                                float *__restrict__ Wd, float *__restrict__ bd) {
     const int total = N_pad * K_pad;
@@ -2314,6 +2362,41 @@ NAQS_API int naqs_net_create_amp_layers(const naqs_net_config_t *cfg, int32_t n_
     return NAQS_OK;
 }
 
+NAQS_API int naqs_net_create_combined(const naqs_net_config_t *cfg, int device, naqs_net_t **out) {
+    if (!cfg || !out) return NAQS_ERR_INVALID;
+    *out = nullptr;
+    if (cfg->aggregate_phase != 0) return NAQS_ERR_UNSUPPORTED;           // (the single-phase family only)
+    if (cfg->amp_hidden > 0 && ((cfg->amp_hidden & 15) || cfg->amp_hidden > 128)) return NAQS_ERR_UNSUPPORTED;
+    if ((cfg->use_phase_spin_sym != 0) != (cfg->use_amp_spin_sym != 0)) return NAQS_ERR_INVALID;      // (nade.py forces them equal)
+    // the per-pair machinery of the aggregate family (amplitude rows + fragments, a second set of raw blocks of the same width,
+    // no phase MLP), of which the combined handle uses the amplitude set and the last raw block
+    naqs_net_config_t c = *cfg;
+    c.aggregate_phase = 1;
+    c.n_phase_hidden = 1;
+    c.phase_hidden[0] = cfg->amp_hidden;
+    naqs_net_t *net = nullptr;
+    int st = naqs_net_create(&c, device, &net);
+    if (st != NAQS_OK) return st;
+    net->cfg = *cfg;
+    net->aggregate = false;
+    net->comb = true;
+    const NetDims &d = net->dims;
+    const int64_t nin = 2 * (d.P - 1), nph = net->dph.n_out_amp;
+    net->comb_amp = net->amp_params;
+    net->comb_head = d.Ha * nin + d.Ha + nph * d.Ha + nph;
+    net->n_params = net->comb_amp + nph * d.Ha + nph;
+    net->amp_params = net->n_params;                      // (no phase layers: every parameter belongs to the blocks)
+    net->ph_params = 0;
+    for (int64_t &o : net->ph_src_off) o = 0;
+    DeviceGuard guard;
+    st = guard.init(device);
+    if (st == NAQS_OK && hipMalloc((void **)&net->d_cflat, (size_t)(net->comb_amp + net->comb_head) * sizeof(float)) != hipSuccess)
+        st = NAQS_ERR_NOMEM;
+    if (st != NAQS_OK) { naqs_net_destroy(net); return st; }
+    *out = net;
+    return NAQS_OK;
+}
+
 NAQS_API int naqs_net_destroy(naqs_net_t *net) {
     if (!net) return NAQS_OK;
     DeviceGuard guard;
@@ -2325,6 +2408,8 @@ NAQS_API int naqs_net_destroy(naqs_net_t *net) {
     if (net->d_wh) (void)hipFree(net->d_wh);
     if (net->d_wamp) (void)hipFree(net->d_wamp);
     if (net->d_wdeep) (void)hipFree(net->d_wdeep);
+    if (net->d_cflat) (void)hipFree(net->d_cflat);
+    if (net->d_cpart) (void)hipFree(net->d_cpart);
     if (net->d_wt) (void)hipFree(net->d_wt);
     if (net->d_scratch) (void)hipFree(net->d_scratch);
     if (net->d_samp) (void)hipFree(net->d_samp);
@@ -2416,7 +2501,29 @@ static int pack_amp_fragments(naqs_net_t *net, const float *flat_dev, hipStream_
     return NAQS_OK;
 }
 
+// combined blocks: the whole re-pack — the flat parameters re-laid out into d_cflat, then the amplitude rows and fragments (byte for
+// byte a plain handle's of the same amplitude rows) and the phase head's rows in one launch
+static int pack_comb(naqs_net_t *net, const float *flat_dev, hipStream_t s) {
+    const NetDims &d = net->dims;
+    const naqs::CombLayout c = naqs::comb_layout(net);
+    NAQS_KLAUNCH(comb_split_kernel, dim3((unsigned)std::min<int64_t>(256, (c.total + 255) / 256)), dim3(256), 0, s, flat_dev, c, net->d_cflat);
+    HIP_TRY(hipGetLastError());
+    AmpSrcOff so0, so1;
+    for (int n = 0; n < MAXP; ++n) { so0.off[n] = net->amp_src_off[n]; so1.off[n] = 0; }
+    so1.off[d.P - 1] = net->comb_amp;
+    const int frag = ((d.Ha >> 4) + (d.Ha >> 5)) * 512;
+    const int total_max = std::max(d.Ha * ((2 * (d.P - 1) + 1 + 5 + 3) & ~3) + 8, net->d_wamp ? frag : 0);
+    net->wamp_fresh = false;
+    NAQS_KLAUNCH(comb_pack_kernel, dim3((total_max + 255) / 256, 2 * d.P + 1), dim3(256), 0, s, net->d_cflat, d, so0, net->d_w, net->d_wamp,
+                       net->dph, so1, net->d_wph);
+    HIP_TRY(hipGetLastError());
+    net->wamp_fresh = net->d_wamp != nullptr;
+    net->have_weights = net->have_amp_weights = net->have_wb = true;
+    return NAQS_OK;
+}
+
 NAQS_API int naqs_net_set_amp_weights(naqs_net_t *net, const float *flat_dev, int64_t count, void *stream) {
+    if (net && net->comb) return naqs_net_set_weights(net, flat_dev, count, stream);     // (every parameter is a block's)
     if (!net || !flat_dev || (count != net->n_params && count != net->amp_params)) return NAQS_ERR_INVALID;
     DeviceGuard guard;
     int st = guard.init(net->device);
@@ -2622,6 +2729,7 @@ NAQS_API int naqs_net_set_weights(naqs_net_t *net, const float *flat_dev, int64_
     net->pack_pending = nullptr;                          // (whatever was pending is superseded by this re-pack)
     net->pack_pending_amp = false;
     if (net->overlap_next_pack != 2) net->amp_head_packed = 0;      // (only naqs_vmc_step's update packs leading pairs itself)
+    if (net->comb) return pack_comb(net, flat_dev, s);      // (nothing is left pending: no launch hosts a share of it)
     if (net->aggregate) {                                   // the phase blocks in the amplitude rows' layout; nothing else to pack
         if (net->dims.P == net->dph.P && (naqs::env_int("NAQS_AGG_MERGE", 7) & 4)) {
             AmpSrcOff so0, so1;
@@ -2670,8 +2778,8 @@ int naqs::net_amp_forward(naqs_net *net, int64_t M, const uint64_t *keys_dev, hi
         if (net->d_scratch) (void)hipFree(net->d_scratch);
         net->d_scratch = nullptr; net->cap_M = 0;
         const int64_t cap = std::max<int64_t>(1024, M + M / 4);
-        // [P][cap] conditional log-amplitudes (+ [P][cap] phases of the per-pair phase blocks)
-        HIP_TRY(hipMalloc((void **)&net->d_scratch, (size_t)cap * d.P * (net->aggregate ? 2 : 1) * sizeof(float)));
+        // [P][cap] conditional log-amplitudes (+ [P][cap] phases of the per-pair phase blocks, or the phase head's in row P - 1)
+        HIP_TRY(hipMalloc((void **)&net->d_scratch, (size_t)cap * d.P * (net->aggregate || net->comb ? 2 : 1) * sizeof(float)));
         net->cap_M = cap;
     }
     if (!launch) return NAQS_OK;
@@ -2746,6 +2854,27 @@ static int agg_logpsi(naqs_net *net, int64_t M, const uint64_t *keys_dev, float 
     return NAQS_OK;
 }
 
+// combined amplitude-phase blocks: the amplitude launch net_amp_forward picks (it also feeds E_loc the keys), the phase head, the sums
+static int comb_logpsi(naqs_net *net, int64_t M, const uint64_t *keys_dev, float *logpsi_dev, hipStream_t s, const ElocFeed &feed) {
+    const NetDims &d = net->dims, &dh = net->dph;
+    const bool prof = net->prof.armed();
+    if (prof) { int stp = net->prof.begin(s); if (stp != NAQS_OK) return stp; }
+    int st = naqs::net_amp_forward(net, M, keys_dev, s, &feed);
+    if (st != NAQS_OK) return st;
+    float *s_head = net->d_scratch + (size_t)d.P * net->cap_M;        // (the head writes its row P - 1)
+    const size_t lds = ((size_t)dh.Ha * ((2 * (dh.P - 1) + 1 + 5 + 3) & ~3) + 8) * sizeof(float);
+    if (lds > 64 * 1024) return NAQS_ERR_UNSUPPORTED;
+    NAQS_KLAUNCH(comb_head_kernel, dim3((unsigned)((M + AMP_TILES * WAVE - 1) / (AMP_TILES * WAVE)), (unsigned)dh.P),
+                       dim3(AMP_TILES * AMP_SPLIT * WAVE), lds, s, dh, net->d_wph, M, keys_dev, s_head);
+    HIP_TRY(hipGetLastError());
+    NAQS_KLAUNCH(comb_finish_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, d.P, M, net->d_scratch,
+                       s_head + (size_t)(dh.P - 1) * M, reinterpret_cast<float2 *>(logpsi_dev), feed);
+    HIP_TRY(hipGetLastError());
+    if (prof) { st = net->prof.end(s); if (st != NAQS_OK) return st; }
+    std::snprintf(net->last_kernel, sizeof(net->last_kernel), "%s + comb_head_kernel + comb_finish_kernel", net->last_amp);
+    return NAQS_OK;
+}
+
 // which form of the log-psi kernel M rows get (net_logpsi_impl; naqs::net_logpsi_form for callers that must know in advance)
 struct FormSel { bool ws = false, ws_split = false; int rb = 1; };
 static FormSel select_form(const naqs_net *net, const int64_t M, const int fmt, const size_t lds_h16, const int rb_max) {
@@ -2779,7 +2908,7 @@ static FormSel select_form(const naqs_net *net, const int64_t M, const int fmt, 
 naqs::PhaseForm naqs::net_logpsi_form(const naqs_net *net, const int64_t M, const bool training) {
     PhaseForm f;
     const NetDims &d = net->dims;
-    if (net->aggregate) return f;
+    if (net->aggregate || net->comb) return f;
     const int fmt = phase_format(d);
     if (fmt == 0) return f;
     const size_t lds_h16 = phase_slab_bytes(d, fmt);
@@ -2809,6 +2938,7 @@ int naqs::net_logpsi_impl(naqs_net *net, int64_t M, const uint64_t *keys_dev, fl
     st = naqs::net_flush_pack(net, s);                     // (the phase share of the last step's re-pack, if no launch hosted it)
     if (st != NAQS_OK) return st;
     if (net->aggregate) return agg_logpsi(net, M, keys_dev, logpsi_dev, s, feed);
+    if (net->comb) return comb_logpsi(net, M, keys_dev, logpsi_dev, s, feed);
     const int fmt = phase_format(d);
     if (fmt != net->packed_fmt) return NAQS_ERR_INVALID;                       // NAQS_PHASE_MODE changed since naqs_net_set_weights
     const bool use_h = fmt != 0;

@@ -183,6 +183,31 @@ __device__ __forceinline__ void amp_conditional(const NetDims &d, int NB, const 
     for (int c = 0; c < 4; ++c) la[c] = ok[c] ? 0.5f * ((a4[c] - m) - ls) : -INFINITY;
 }
 
+// ---- combined amplitude-phase blocks (naqs_net_create_combined) ----
+// The flat parameters are the state_dict's: blocks 0 .. P-2 as in a plain handle, then the last block
+// W1 [Ha][nin] | b1 [Ha] | W2 [na + nph][Ha] | b2 [na + nph] (amplitude rows first).  The kernels read two re-laid-out copies:
+// the amplitude blocks in the plain layout (last block W1 | b1 | W2 [na][Ha] | b2 [na]) and the phase head
+// W1 | b1 | W2 [nph][Ha] | b2 [nph] behind them.
+struct CombLayout {
+    int64_t last = 0;          // offset of the last block (the same in both layouts)
+    int64_t amp = 0;           // floats of the amplitude blocks in the plain layout = offset of the head in the copy
+    int64_t total = 0;         // floats of the flat parameters
+    int32_t Ha = 0, nin = 0, na = 0, nph = 0;
+};
+// flat index e -> its place in the plain amplitude layout (pa) and in the head (ph, relative to the head); -1: none.  W1 and b1 of
+// the last block have both (the head shares them), every other parameter exactly one.
+__host__ __device__ inline void comb_src(const CombLayout &c, const int64_t e, int64_t &pa, int64_t &ph) {
+    pa = -1; ph = -1;
+    if (e < c.last) { pa = e; return; }
+    const int64_t r = e - c.last;
+    const int64_t w1b1 = (int64_t)c.Ha * c.nin + c.Ha, w2a = (int64_t)c.na * c.Ha, w2p = (int64_t)c.nph * c.Ha;
+    if (r < w1b1) { pa = e; ph = r; }
+    else if (r < w1b1 + w2a) pa = e;
+    else if (r < w1b1 + w2a + w2p) ph = r - w2a;
+    else if (r < w1b1 + w2a + w2p + c.na) pa = c.last + w1b1 + w2a + (r - w1b1 - w2a - w2p);
+    else ph = w1b1 + w2p + (r - w1b1 - w2a - w2p - c.na);
+}
+
 // log-amplitude of the realised outcome
 __device__ __forceinline__ float amp_finish(const NetDims &d, int NB, const float (&o)[5], uint32_t abits,
                                             uint32_t bbits, int occ) {
@@ -261,6 +286,14 @@ struct naqs_net {
     int64_t deep_off[naqs::MAXP] = {};
     int64_t deep_floats = 0;
     char last_deep[96] = {0};               // the deep launches of the last sampler / backward call (naqs_net_last_kernel)
+    // combined amplitude-phase blocks (naqs_net_create_combined): the last block's output layer also carries the phase rows.
+    // dims / d_w / d_wamp hold the amplitude blocks exactly as a plain handle's (the sampler runs unchanged); dph describes the
+    // "phase head" — the last block's W1, b1 and phase rows as a raw block of pair P - 1, packed at d_wph + dph.amp_off[P - 1].
+    // d_cflat = [amplitude blocks in the plain layout (comb_amp floats) | the head (comb_head floats)], re-laid out from the flat
+    // parameters by every re-pack; d_cpart: the backward's per-workgroup partial sums in d_cflat's layout (naqs_grad.hip)
+    bool comb = false, comb_attr_set = false;
+    int64_t comb_amp = 0, comb_head = 0;
+    float *d_cflat = nullptr, *d_cpart = nullptr;
     bool aggregate = false;
     naqs::NetDims dph{};
     int64_t ph_src_off[naqs::MAXP] = {};          // per pair: offset of its phase block in the flat source
@@ -415,6 +448,18 @@ inline AdamArgs adam_args(float *p, float *m, float *v, double lr, double beta1,
     a.eps = (float)eps; a.weight_decay = (float)weight_decay;
     return a;
 }
+inline CombLayout comb_layout(const naqs_net *net) {
+    const NetDims &d = net->dims;
+    CombLayout c;
+    c.last = net->amp_src_off[d.P - 1]; c.amp = net->comb_amp; c.total = net->n_params;
+    c.Ha = d.Ha; c.nin = 2 * (d.P - 1); c.na = d.n_out_amp; c.nph = net->dph.n_out_amp;
+    return c;
+}
+// naqs_grad.hip: the combined handle's backward — amplitude blocks on g[:, 0] (g_stride 2) or g (g_stride 1), with_head: the phase
+// head on g[:, 1] — reduced in fixed order into grad_dev in the flat layout (the head's W1 / b1 added to the last block's), and
+// with `adam` the update of every element in the same launch
+int net_comb_backward(naqs_net *net, int64_t M, const uint64_t *keys_dev, const float *g_dev, int g_stride, bool with_head,
+                      float *grad_dev, const AdamArgs *adam, hipStream_t s);
 #if defined(__HIPCC__)
 // (pi, m0, v0: the element's parameter and moments as loaded by the caller — so that it can have them in flight under other loads)
 __device__ __forceinline__ float adam_update_loaded(const AdamArgs &a, const int64_t i, float gi, const float pi, const float m0, const float v0) {

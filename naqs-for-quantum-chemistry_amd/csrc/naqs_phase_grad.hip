@@ -725,7 +725,7 @@ NAQS_API int naqs_net_train_forward(naqs_net_t *net, int64_t M, const uint64_t *
     DeviceGuard guard;
     int st = guard.init(net->device);
     if (st != NAQS_OK) return st;
-    if (net->aggregate) {                                   // the per-pair blocks are recomputed by the backward pass: nothing to keep
+    if (net->aggregate || net->comb) {                      // the per-pair blocks are recomputed by the backward pass: nothing to keep
         naqs::ElocFeed none{};
         return naqs::net_logpsi_impl(net, M, keys_dev, logpsi_dev, stream, none, naqs::PhaseSave{});
     }
@@ -760,7 +760,7 @@ NAQS_API int naqs_net_train_forward_eloc(naqs_net_t *net, naqs_ham_t *ham, int64
         return NAQS_OK;
     }
     naqs::PhaseSave save;
-    if (!net->aggregate) {
+    if (!net->aggregate && !net->comb) {
         st = ensure_train_scratch(net, M);
         if (st != NAQS_OK) return st;
         const TrainLayout L = train_layout(net, net->train_cap);
@@ -900,7 +900,7 @@ static int train_backward_impl(naqs_net_t *net, int64_t M, const uint64_t *keys_
         if (stj != NAQS_OK) return stj;
     }
     if (!net->have_weights || !net->have_wb) return NAQS_ERR_INVALID;
-    if (!net->aggregate && (M > net->train_cap || !net->d_train)) return NAQS_ERR_INVALID;   // naqs_net_train_forward of the same batch comes first
+    if (!net->aggregate && !net->comb && (M > net->train_cap || !net->d_train)) return NAQS_ERR_INVALID;   // naqs_net_train_forward of the same batch comes first
     DeviceGuard guard;
     int st = guard.init(net->device);
     if (st != NAQS_OK) return st;
@@ -910,6 +910,9 @@ static int train_backward_impl(naqs_net_t *net, int64_t M, const uint64_t *keys_
         HIP_TRY(hipMemsetAsync(grad_dev, 0, (size_t)net->n_params * sizeof(float), s));
         return NAQS_OK;
     }
+    // combined amplitude-phase blocks: the amplitude blocks on g[:, 0] and the phase head on g[:, 1] in one launch, then the
+    // fixed-order reduction into the flat layout (+ Adam) in another (naqs_grad.hip)
+    if (net->comb) return naqs::net_comb_backward(net, M, keys_dev, g_dev, 2, true, grad_dev, adam, s);
     GradFinish F;
     if (net->aggregate) {
         // both sets of per-pair blocks through the same backward kernel: amplitude blocks on g[:, 0], phase blocks (raw
@@ -1181,7 +1184,7 @@ NAQS_API int naqs_vmc_step(naqs_net_t *net, naqs_ham_t *ham, int64_t n_samples, 
         bool launched = false; int64_t rows = 0; naqs::ElocFeed feed{}; naqs::PhaseForm form;
         int operator()() override {
             const int64_t hint = net->spec_hint;
-            if (hint <= 0 || net->aggregate || !ham || !logpsi || naqs::env_int("NAQS_SPEC_FORWARD", 1) == 0) return NAQS_OK;
+            if (hint <= 0 || net->aggregate || net->comb || !ham || !logpsi || naqs::env_int("NAQS_SPEC_FORWARD", 1) == 0) return NAQS_OK;
             if (naqs::ham_device(ham) != net->device) return NAQS_OK;
             int64_t cover = std::min<int64_t>(max_unique, hint + std::max<int64_t>(64, hint / 8));
             if (naqs::env_int("NAQS_DEBUG_SPEC_SHRINK", 0) != 0) cover = std::max<int64_t>(16, hint / 2);      // (tests: a launch that does not fit)
@@ -1361,6 +1364,7 @@ NAQS_API int naqs_vmc_shard_sample_forward(naqs_net_t *net, int64_t n_samples, u
                                            void *stream) {
     if (!net || !info_host || !logpsi_shard_dev || world < 1 || rank < 0 || rank >= world) return NAQS_ERR_INVALID;
     info_host[2] = 0;
+    if (net->comb) return NAQS_ERR_UNSUPPORTED;           // (combined blocks: the replicated step only)
     int64_t info2[2] = {0, 0};
     DeviceGuard guard;
     int st = guard.init(net->device);
@@ -1385,6 +1389,7 @@ NAQS_API int naqs_vmc_shard_update(naqs_net_t *net, const float *grad_dev, float
                                    double lr, double beta1, double beta2, double eps, double weight_decay, int64_t adam_step,
                                    void *stream) {
     if (!net || !grad_dev || !param_dev || !exp_avg_dev || !exp_avg_sq_dev || adam_step < 1) return NAQS_ERR_INVALID;
+    if (net->comb) return NAQS_ERR_UNSUPPORTED;           // (combined blocks: the replicated step only)
     DeviceGuard guard;
     int st = guard.init(net->device);
     if (st != NAQS_OK) return st;
@@ -1403,7 +1408,7 @@ static int train_backward_vmc_impl(naqs_net_t *net, int64_t M, const uint64_t *k
                                    const double *w_dev, const double *sums_dev, float *g_dev, double *ev_dev, float *grad_dev,
                                    void *stream, const naqs::AdamArgs *adam, bool form_sums) {
     if (!net || !sums_dev || !ev_dev || !g_dev || (M > 0 && (!eloc_dev || !w_dev))) return NAQS_ERR_INVALID;
-    if (net->aggregate || M == 0) {                   // per-pair phase blocks (or nothing to do): the two separate calls
+    if (net->aggregate || net->comb || M == 0) {      // per-pair phase blocks, combined blocks (or nothing to do): the two separate calls
         int st = naqs_vmc_loss_grad_ev(M, eloc_dev, w_dev, sums_dev, g_dev, ev_dev, stream);
         if (st != NAQS_OK) return st;
         return train_backward_impl(net, M, keys_dev, g_dev, grad_dev, stream, nullptr, adam);

@@ -47,6 +47,7 @@ SIGNATURES = {
     "naqs_net_prof_stride": (ctypes.c_int, [c_vp, ctypes.c_int]),
     "naqs_net_create": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.POINTER(c_vp)]),
     "naqs_net_create_amp_layers": (ctypes.c_int, [c_vp, ctypes.c_int32, ctypes.c_int, ctypes.POINTER(c_vp)]),
+    "naqs_net_create_combined": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.POINTER(c_vp)]),
     "naqs_net_destroy": (ctypes.c_int, [c_vp]),
     "naqs_net_param_count": (ctypes.c_int, [c_vp, ctypes.POINTER(c_i64)]),
     "naqs_net_set_weights": (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp]),

@@ -8,9 +8,12 @@ Supported architecture families:
   * the reference's default ansatz (experiments/run.py:11-31): the same amplitude blocks and one phase block per orbital
     pair (``aggregate_phase=True``), each with one hidden layer (multiple of 16, <= 128 units);
 both with or without the phase spin symmetry (``-phase_sym``, nade.py:281, 507-533, 590-610: spin-ordered inputs of the phase
-block(s), 3 outputs, the sign shift — since round 5), <= 16 orbital pairs.  Anything else (combined amplitude-phase blocks,
-look-up-table blocks) raises ``NotImplementedError`` — callers then stay on the PyTorch modules (same numbers, more launches),
-and ``wavefunction.fused()`` says so on stdout.
+block(s), 3 outputs, the sign shift — since round 5);
+  * combined amplitude-phase blocks with a single phase (``-single_phase -comb_amp_phase``, nade.py:294-303, 555-560): no phase
+    MLP, the last one-hidden-layer amplitude block's output layer also carries the phase rows (``naqs_net_create_combined``);
+<= 16 orbital pairs.  Anything else (combined blocks with ``aggregate_phase=True`` or deeper blocks, look-up-table blocks) raises
+``NotImplementedError`` — callers then stay on the PyTorch modules (same numbers, more launches), and ``wavefunction.fused()``
+says so on stdout.
 """
 import ctypes
 import os
@@ -65,14 +68,16 @@ class FusedLogPsi:
             raise _lib.NaqsError("FusedLogPsi needs the network on a HIP device (no CPU fallback)")
         self.aggregate = bool(m.aggregate_phase)
         self.phase_sym = bool(getattr(m, "use_phase_spin_sym", False))
-        if getattr(m, "combined_amp_phase_blocks", False):
-            raise NotImplementedError("fused log-psi: combined amplitude-phase blocks (no published script uses them) run as "
-                                      "PyTorch modules")
-        if len(m.phase_layers) != (m.P if self.aggregate else 1):
-            raise NotImplementedError("fused log-psi: unexpected number of phase blocks")
+        # -comb_amp_phase: the single-phase form with one hidden layer per block runs on the kernels (naqs_net_create_combined)
+        self.comb = bool(getattr(m, "combined_amp_phase_blocks", False))
         amp_lin = m.amp_layers[0].linears()
         # 1 hidden layer; or 2..4 of one width with a single phase block (naqs_net_create_amp_layers)
         self.amp_depth = len(amp_lin) - 1
+        if self.comb and (self.aggregate or self.amp_depth != 1):
+            raise NotImplementedError("fused log-psi: combined amplitude-phase blocks with aggregate_phase=True or more than one "
+                                      "hidden layer (no published script uses them) run as PyTorch modules")
+        if len(m.phase_layers) != (0 if self.comb else (m.P if self.aggregate else 1)):
+            raise NotImplementedError("fused log-psi: unexpected number of phase blocks")
         deep_ok = (not self.aggregate and 2 <= self.amp_depth <= _lib.NET_MAX_AMP_LAYERS
                    and len({lin.out_features for lin in amp_lin[:-1]}) == 1)
         if self.amp_depth != 1 and not deep_ok:
@@ -82,9 +87,10 @@ class FusedLogPsi:
             raise NotImplementedError(f"fused log-psi: amplitude hidden width {ha} (a multiple of 16, <= 128, is supported)")
         if m.P > _lib.NET_MAX_PAIRS or m.P < 2:
             raise NotImplementedError("fused log-psi: 2..16 orbital pairs")
-        phase_lin = m.phase_layers[0].linears()
-        hidden = [lin.out_features for lin in phase_lin[:-1]]
-        if self.aggregate:
+        hidden = [] if self.comb else [lin.out_features for lin in m.phase_layers[0].linears()[:-1]]
+        if self.comb:
+            pass
+        elif self.aggregate:
             if len(hidden) != 1 or hidden[0] % 16 or hidden[0] > 128:
                 raise NotImplementedError("fused log-psi: aggregate_phase=True with other than one phase hidden layer per "
                                           f"block of a multiple of 16, <= 128 units (got {hidden})")
@@ -108,7 +114,10 @@ class FusedLogPsi:
         cfg.aggregate_phase = int(self.aggregate)
         cfg.use_phase_spin_sym = int(self.phase_sym)          # -phase_sym with one phase block (nade.py:281, 507-533, 590-610)
         self._h = ctypes.c_void_p(None)
-        if self.amp_depth == 1:
+        if self.comb:
+            st = self._lib.naqs_net_create_combined(ctypes.byref(cfg), self.device.index or 0, ctypes.byref(self._h))
+            _lib.check(st, "naqs_net_create_combined")
+        elif self.amp_depth == 1:
             st = self._lib.naqs_net_create(ctypes.byref(cfg), self.device.index or 0, ctypes.byref(self._h))
             _lib.check(st, "naqs_net_create")
         else:
@@ -120,19 +129,20 @@ class FusedLogPsi:
         self._samp = None
         self._grad_flat, self._grad_views = None, None
         self.train_mode = os.environ.get("NAQS_TRAIN_MODE", "hip")     # "hip" | "blas" (phase MLP through torch/rocBLAS)
-        if self.aggregate or self.phase_sym:
-            self.train_mode = "hip"                                     # (the per-pair phase blocks / spin-ordered inputs have no BLAS formulation here)
+        if self.aggregate or self.phase_sym or self.comb:
+            self.train_mode = "hip"                                     # (the per-pair phase blocks / spin-ordered inputs / phase rows have no BLAS formulation here)
         assert self.n_params == sum(p.numel() for p in m.parameters()), "parameter layout mismatch"
         _lib.check(self._lib.naqs_net_amp_param_count(self._h, ctypes.byref(n)), "naqs_net_amp_param_count")
         self.n_amp_params = n.value
         self._amp_params = [p for blk in m.amp_layers for p in blk.parameters()]
         assert self.n_amp_params == sum(p.numel() for p in self._amp_params), "amplitude parameter layout mismatch"
-        # key bits feeding the phase block (alpha then beta occupations of model pairs 0..P-2) and the last pair's outcome
-        q2m = [int(q) for q in wf.qubit2model_permutation]
-        P = m.P
-        self._phase_shifts = torch.tensor([q2m[2 * k] for k in range(P - 1)] + [q2m[2 * k + 1] for k in range(P - 1)],
-                                          dtype=torch.int64, device=self.device)
-        self._last_a, self._last_b = q2m[2 * (P - 1)], q2m[2 * (P - 1) + 1]
+        if not self.comb:
+            # key bits feeding the phase block (alpha then beta occupations of model pairs 0..P-2) and the last pair's outcome
+            q2m = [int(q) for q in wf.qubit2model_permutation]
+            P = m.P
+            self._phase_shifts = torch.tensor([q2m[2 * k] for k in range(P - 1)] + [q2m[2 * k + 1] for k in range(P - 1)],
+                                              dtype=torch.int64, device=self.device)
+            self._last_a, self._last_b = q2m[2 * (P - 1)], q2m[2 * (P - 1) + 1]
         self.refresh()
 
     def refresh(self, amp_only=False):
@@ -153,9 +163,9 @@ class FusedLogPsi:
         pair, the phase MLP (three Linear layers) through PyTorch/rocBLAS.  Same function of the parameters as
         ``wavefunction.log_psi(states)``."""
         m = self.wf.model
-        if self.aggregate or self.phase_sym:
-            raise NotImplementedError("log_psi_train (autograd.Function form) for aggregate_phase / phase-symmetric networks: use "
-                                      "forward_saved / backward_saved")
+        if self.aggregate or self.phase_sym or self.comb:
+            raise NotImplementedError("log_psi_train (autograd.Function form) for aggregate_phase / phase-symmetric / combined-block "
+                                      "networks: use forward_saved / backward_saved")
         keys = keys.contiguous()
         log_amp = _LogAmp.apply(self, keys, *self._amp_params)
         x = ((keys.unsqueeze(-1) >> self._phase_shifts) & 1).to(torch.float32).mul_(2.0).sub_(1.0)

@@ -277,6 +277,9 @@ class OptimizerBase:
                     mode = "sharded" if (M >= self.shard_min_table and M // world >= self.shard_min_rows) else "replicated"
             elif self._dist_mode == "sharded" and mode != "sharded":
                 self._check_shards()
+            m = self.wavefunction.model
+            if getattr(m, "combined_amp_phase_blocks", False) and not m.aggregate_phase:
+                mode = "replicated"          # -single_phase -comb_amp_phase: no sharded step (naqs_vmc_shard_* refuse its handles)
         if mode != self._dist_mode:
             if dist is not None:
                 self.dist_mode_log.append((self.n_steps, mode))
@@ -473,7 +476,7 @@ class OptimizerBase:
             elif fused is not None and regularisation_loss is None and not self.normalize_grads:
                 # HIP amplitude forward/backward + explicit chain rule of the phase MLP: no autograd graph at all
                 lp_mine, saved = fused.forward_saved(keys[b:e_])
-            elif fused is not None and not fused.aggregate:     # same kernels behind a torch.autograd.Function
+            elif fused is not None and not fused.aggregate and not fused.comb:     # same kernels behind a torch.autograd.Function
                 lp_mine = fused.log_psi_train(keys[b:e_])
             else:
                 lp_mine = self.wavefunction.log_psi(states[b:e_]).reshape(-1, 2)
