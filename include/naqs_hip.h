@@ -198,7 +198,8 @@ int naqs_prof_stride(naqs_ham_t *h, int stride);
  * _forward_predict (src/naqs/network/nade.py:738-770) for the published architecture family:
  * one amplitude MLP per orbital pair (one hidden layer; 2..4 of one width through naqs_net_create_amp_layers), and either
  * a single phase MLP on the last pair (aggregate_phase = False: -single_phase, the published runs) or one single-hidden-layer
- * phase block per pair whose outputs are summed (aggregate_phase = True: the reference's default), or no phase MLP and the
+ * phase block per pair whose outputs are summed (aggregate_phase = True: the reference's default; amplitude and phase blocks
+ * both of 2..4 hidden layers through naqs_net_create_agg_layers), or no phase MLP and the
  * last amplitude block's output layer carrying the phase rows (naqs_net_create_combined: -single_phase -comb_amp_phase);
  * SoftmaxLogProbAmps amplitudes, with or without the phase spin symmetry.
  * ============================================================================================== */
@@ -219,7 +220,8 @@ typedef struct naqs_net_config {
     int32_t aggregate_phase;          /* 0: one phase MLP on the last pair (the published runs, -single_phase);
                                        * 1: one phase block per orbital pair, phases summed — the reference's default
                                        *    (experiments/run.py:31, nade.py:556-569): every block is
-                                       *    Linear(max(1, 2n), phase_hidden[0]) + ReLU + Linear(phase_hidden[0], 4); n_phase_hidden must be 1 */
+                                       *    Linear(max(1, 2n), phase_hidden[0]) + ReLU + Linear(phase_hidden[0], 4); n_phase_hidden must be 1
+                                       *    (naqs_net_create_agg_layers: 1..4, the amplitude blocks' depth) */
     int32_t use_phase_spin_sym;       /* 1 (-phase_sym, nade.py:281, 507-533, 590-610; ABI 7): the phase block reads spin-ordered inputs
                                        *    (alpha and beta strings of the first P-1 pairs exchanged when idx(alpha) > idx(beta)), has
                                        *    3 outputs for |00>, |01> = |10>, |11>, and the phase gets + pi (N_01 mod 2) where
@@ -249,6 +251,20 @@ int naqs_net_create_amp_layers(const naqs_net_config_t *cfg, int32_t n_amp_hidde
  * amplitude rows draws; naqs_net_amp_backward differentiates log|psi| only (zero gradient for the phase rows); naqs_vmc_step /
  * naqs_vmc_run take the non-speculative order; the naqs_vmc_shard_* calls return NAQS_ERR_UNSUPPORTED. */
 int naqs_net_create_combined(const naqs_net_config_t *cfg, int device, naqs_net_t **out);
+/* naqs_net_create for the aggregate phase (aggregate_phase = 1, the reference's default ansatz) with every block of n_hidden hidden
+ * layers — the reference's -n_layer, which -n_layer_phase follows by default: amplitude blocks of cfg->amp_hidden units per layer,
+ * per-pair phase blocks of cfg->phase_hidden[0] units per layer (each a multiple of 16, <= 128; the two may differ).
+ * n_hidden == 1 is naqs_net_create.  NAQS_ERR_INVALID: cfg or out null, n_hidden outside 1..4 (or an odd n_qubits);
+ * NAQS_ERR_UNSUPPORTED: aggregate_phase = 0 (naqs_net_create_amp_layers' family), cfg->n_phase_hidden != n_hidden,
+ * phase_hidden[0 .. n_hidden - 1] not all equal, a width outside the set above, or P outside 2..16 — all of them before the device
+ * is looked at.  The flat layout is the state_dict order: the amplitude blocks block by block (W1, b1, W2, b2, ..., Wo, bo as in
+ * naqs_net_create_amp_layers), then the phase blocks the same way (Wo [4][Hp], or [3][Hp] with use_phase_spin_sym);
+ * naqs_net_param_count counts both, naqs_net_amp_param_count the amplitude blocks.  The amplitude set is byte for byte a
+ * naqs_net_create_amp_layers handle's, so the sampler, naqs_net_logamp and naqs_net_amp_backward run as for it;
+ * naqs_net_set_amp_weights packs that set only.  naqs_net_last_kernel names the forward form ("agg_deep_kernel<CT, L=..>" when
+ * both widths are equal, else "amp_deep_kernel<..> + amp_deep_raw_kernel<..>", then "+ agg_finish_kernel") and the last backward.
+ * naqs_vmc_step / naqs_vmc_run take the non-speculative order; the naqs_vmc_shard_* calls return NAQS_ERR_UNSUPPORTED. */
+int naqs_net_create_agg_layers(const naqs_net_config_t *cfg, int32_t n_hidden, int device, naqs_net_t **out);
 int naqs_net_destroy(naqs_net_t *net);
 /* Number of float parameters expected by naqs_net_set_weights: the reference's state_dict order,
  * flattened (amp_layers.0.layers.0.0.weight, .bias, amp_layers.0.layers.1.0.weight, .bias, ...,

@@ -50,6 +50,13 @@ inline DeepAmp deep_amp(const naqs_net *net) {
     for (int n = 0; n < MAXP; ++n) { a.off[n] = net->deep_off[n]; a.src[n] = net->amp_src_off[n]; }
     return a;
 }
+// ... and of its deep phase blocks (naqs_net_create_agg_layers: the same depth, packed into d_wph)
+inline DeepAmp deep_phase(const naqs_net *net) {
+    DeepAmp a;
+    a.L = net->amp_depth;
+    for (int n = 0; n < MAXP; ++n) { a.off[n] = net->ph_deep_off[n]; a.src[n] = net->ph_src_off[n]; }
+    return a;
+}
 
 #if defined(__HIPCC__)
 
@@ -123,14 +130,15 @@ __device__ __forceinline__ void deep_dense(const float *__restrict__ wl, int row
 // One wave, one (tile of 16 samples, pair n) item through all L hidden layers: the block's raw outputs -> outs[sample][8]
 // (entries >= nout are 0).  ab: the occupation strings (alpha | beta << 16) of sample lane & 15.  wp: pair n's packed block.
 // hs (optional): per hidden layer l the post-ReLU activations, hs[l - 1][unit * hs_ld + sample] (the backward pass).
-template <int CT>
+// RAW: a phase block of an aggregate-phase network (d = net->dph): it orders its inputs under d.phase_sym, not d.sym.
+template <int CT, bool RAW = false>
 __device__ __forceinline__ void amp_deep_item(const NetDims &d, const float *__restrict__ wp, int L, int n, uint32_t ab, int lane,
                                               float *__restrict__ outs, float *hs = nullptr, int hs_ld = 0, int hs_layer = 0) {
     constexpr int Ha = CT * 16;
     const int s = lane & 15, kq = lane >> 4;
     const uint32_t mask = (1u << n) - 1u;
     const uint32_t abits = ab & mask, bbits = (ab >> 16) & mask;
-    const bool swap = d.sym && abits > bbits;                                   // nade.py:519-530
+    const bool swap = (RAW ? d.phase_sym : d.sym) && abits > bbits;             // nade.py:519-530
     const uint32_t first = swap ? bbits : abits, second = swap ? abits : bbits;
     f32x4 h[CT];
     deep_layer1<CT>(wp, n, first, second, lane, h);
@@ -193,10 +201,13 @@ __device__ __forceinline__ void deep_gemm(int J, int K, FA fa, FB fb, float *__r
     }
 }
 
-template <int CT>
+// RAW: a phase block of an aggregate-phase network (d = net->dph): d out[c] = g_i [c == phase_out_row(occ)], no conditional, and
+// the inputs in phase_sym order (the depth-1 blocks' raw mode, naqs_amp_backward.hpp).  g_stride 2: a column of the loss gradient [M][2].
+template <int CT, bool RAW = false>
 __device__ __forceinline__ void amp_deep_backward_pair(const NetDims &d, const float *__restrict__ wp, const int L, const int n,
                                                        const int64_t M, const uint64_t *__restrict__ keys, const float *__restrict__ g,
-                                                       float *__restrict__ out, float *smem, const int wg, const int n_wgs) {
+                                                       float *__restrict__ out, float *smem, const int wg, const int n_wgs,
+                                                       const int g_stride = 1) {
     constexpr int Ha = CT * 16, LD = DGT + 1;
     const int layer = Ha * LD, nout = d.n_out_amp, nin = n == 0 ? 1 : 2 * n;
     float *s_h = smem;                                                  // [L][Ha][LD]
@@ -218,15 +229,22 @@ __device__ __forceinline__ void amp_deep_backward_pair(const NetDims &d, const f
         }
         const int occ = (int)((key >> d.qa[n]) & 1ull) + 2 * (int)((key >> d.qb[n]) & 1ull);
         float *outs = s_outs + wave * 128;
-        amp_deep_item<CT>(d, wp, L, n, abits | (bbits << 16), lane, outs, s_h + 16 * wave, LD, layer);
+        amp_deep_item<CT, RAW>(d, wp, L, n, abits | (bbits << 16), lane, outs, s_h + 16 * wave, LD, layer);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (kq == 0) {                                      // lanes 0..15: d log-amp / d outputs of their sample (as amp_backward_pair)
+        if (kq == 0 && RAW) {                               // lanes 0..15: d phase / d outputs of their sample
+            const float gi = valid ? g[i * g_stride] : 0.0f;
+            const int row = naqs::phase_out_row(d, occ);
+#pragma unroll
+            for (int c = 0; c < 8; ++c) s_do[c * DGT + col] = valid && c == row ? gi : 0.0f;
+            const bool swap = d.phase_sym && abits > bbits;
+            s_x[col] = (swap ? bbits : abits) | ((swap ? abits : bbits) << 16);
+        } else if (kq == 0) {                               // lanes 0..15: d log-amp / d outputs of their sample (as amp_backward_pair)
             float o[5];
 #pragma unroll
             for (int c = 0; c < 5; ++c) o[c] = outs[s * 8 + c];
-            const float gi = valid ? g[i] : 0.0f;
+            const float gi = valid ? g[i * g_stride] : 0.0f;
             float la[4];
             bool ok[4];
             naqs::amp_conditional<true>(d, n, o, abits, bbits, la, ok);

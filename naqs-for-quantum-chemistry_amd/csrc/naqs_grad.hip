@@ -69,6 +69,42 @@ __global__ __launch_bounds__(naqs::DBW * 64) void amp_deep_backward_kernel(const
     naqs::amp_deep_backward_pair<CT>(d, wdeep + da.off[n], da.L, n, M, keys, g, out, smem, (int)blockIdx.x, (int)gridDim.x);
 }
 
+// aggregate phase with deep blocks (naqs_net_create_agg_layers): the phase blocks (raw, d = net->dph) on g with stride g_stride, the
+// same partial-sum layout
+template <int CT>
+__global__ __launch_bounds__(naqs::DBW * 64) void amp_deep_backward_raw_kernel(const NetDims d, const float *__restrict__ wdeep,
+                                                                             const naqs::DeepAmp da, const int64_t M,
+                                                                             const uint64_t *__restrict__ keys, const float *__restrict__ g,
+                                                                             const int g_stride, float *__restrict__ partial,
+                                                                             const int64_t partial_stride) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int n = blockIdx.y;
+    float *out = partial + (int64_t)blockIdx.x * partial_stride + (da.src[n] - da.src[0]);
+    naqs::amp_deep_backward_pair<CT, true>(d, wdeep + da.off[n], da.L, n, M, keys, g, out, smem, (int)blockIdx.x, (int)gridDim.x, g_stride);
+}
+
+// ... and both sets in ONE launch when Ha == Hp: the amplitude blocks (blockIdx.z == 0, on g[:, 0]) and the phase blocks (1, raw,
+// on g[:, 1]), the loss gradient read in place (stride 2); each into its half of the partial-sum scratch
+template <int CT>
+__global__ __launch_bounds__(naqs::DBW * 64) void agg_deep_backward_kernel(const NetDims d0, const float *__restrict__ w0, const naqs::DeepAmp da0,
+                                                                         float *__restrict__ partial0, const NetDims d1,
+                                                                         const float *__restrict__ w1, const naqs::DeepAmp da1,
+                                                                         float *__restrict__ partial1, const int64_t M,
+                                                                         const uint64_t *__restrict__ keys, const float *__restrict__ g_amp,
+                                                                         const float *__restrict__ g_ph, const int g_stride,
+                                                                         const int64_t partial_stride) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int n = blockIdx.y;
+    if (blockIdx.z == 0)
+        naqs::amp_deep_backward_pair<CT, false>(d0, w0 + da0.off[n], da0.L, n, M, keys, g_amp,
+                                                partial0 + (int64_t)blockIdx.x * partial_stride + (da0.src[n] - da0.src[0]), smem,
+                                                (int)blockIdx.x, (int)gridDim.x, g_stride);
+    else
+        naqs::amp_deep_backward_pair<CT, true>(d1, w1 + da1.off[n], da1.L, n, M, keys, g_ph,
+                                               partial1 + (int64_t)blockIdx.x * partial_stride + (da1.src[n] - da1.src[0]), smem,
+                                               (int)blockIdx.x, (int)gridDim.x, g_stride);
+}
+
 // aggregate_phase: the amplitude blocks (blockIdx.z == 0, on g[:, 0]) and the per-pair phase blocks (1, raw, on g[:, 1]) in ONE
 // launch; the loss gradient's two columns are read in place (stride 2), no split launch in front
 // (the two sets' descriptions are separate kernel arguments: nested in a struct their dynamically indexed tables end up in
@@ -316,6 +352,23 @@ int naqs::net_blocks_backward(naqs_net *net, const NetDims &d, const float *w, c
         HIP_TRY(hipGetLastError());
         std::snprintf(net->last_deep, sizeof(net->last_deep), "backward: amp_deep_backward_kernel<%d, L=%d>", d.Ha >> 4,
                       net->amp_depth);
+    } else if (net->amp_depth > 1 && raw == 1 && net->aggregate && &d == &net->dph) {      // deep phase blocks (naqs_net_create_agg_layers)
+        const size_t lds_d = naqs::deep_bw_smem_floats(d.Ha, net->amp_depth) * sizeof(float);
+        if (lds_d > 156 * 1024) return NAQS_ERR_UNSUPPORTED;
+        const naqs::DeepAmp da = naqs::deep_phase(net);
+        switch (d.Ha >> 4) {
+#define NAQS_DEEP(C) case C:                                                                                                              \
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&amp_deep_backward_raw_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024)); \
+            NAQS_KLAUNCH(amp_deep_backward_raw_kernel<C>, dim3((unsigned)n_wg, (unsigned)d.P), dim3(naqs::DBW * WAVE), lds_d, s, d, net->d_wph, da, M, \
+                         keys_dev, g_dev, 1, gpart, stride);                                                                              \
+            break;
+            NAQS_DEEP(1) NAQS_DEEP(2) NAQS_DEEP(3) NAQS_DEEP(4) NAQS_DEEP(5) NAQS_DEEP(6) NAQS_DEEP(7) NAQS_DEEP(8)
+#undef NAQS_DEEP
+            default: return NAQS_ERR_UNSUPPORTED;
+        }
+        HIP_TRY(hipGetLastError());
+        std::snprintf(net->last_deep, sizeof(net->last_deep), "backward: amp_deep_backward_kernel<%d, L=%d> + amp_deep_backward_raw_kernel<%d, L=%d>",
+                      net->dims.Ha >> 4, net->amp_depth, d.Ha >> 4, net->amp_depth);
     } else {
         const int NW = d.Ha >> 4;
         const size_t lds = naqs::ampbw::smem_floats(d) * sizeof(float);
@@ -365,6 +418,34 @@ int naqs::net_blocks_backward2(naqs_net *net, int64_t M, const uint64_t *keys_de
                                BlockReduceJob jobs[2], hipStream_t s) {
     const NetDims &d0 = net->dims, &d1 = net->dph;
     if (d0.Ha != d1.Ha || d0.P != d1.P || M <= 0) return NAQS_ERR_INVALID;
+    if (net->amp_depth > 1) {                     // deep blocks (naqs_net_create_agg_layers): agg_deep_backward_kernel, same partials
+        if (d0.Ha > 128 || (d0.Ha & 15) || !net->aggregate) return NAQS_ERR_UNSUPPORTED;
+        const int n_wg = (int)std::min<int64_t>(MAX_TILE_WGS, (M + GT - 1) / GT);
+        const int64_t stride = (std::max(net->amp_params, net->ph_params) + 3) & ~3ll;
+        if (!net->d_gpart) HIP_TRY(hipMalloc((void **)&net->d_gpart, 2 * (size_t)MAX_TILE_WGS * stride * sizeof(float)));
+        const size_t lds_d = naqs::deep_bw_smem_floats(d0.Ha, net->amp_depth) * sizeof(float);
+        if (lds_d > 156 * 1024) return NAQS_ERR_UNSUPPORTED;
+        jobs[0].count = net->amp_params; jobs[1].count = net->ph_params;
+        for (int k = 0; k < 2; ++k) {
+            jobs[k].stride = stride; jobs[k].n_partials = n_wg;
+            jobs[k].partial = net->d_gpart + (k ? (size_t)MAX_TILE_WGS * stride : 0);
+        }
+        const naqs::DeepAmp da0 = naqs::deep_amp(net), da1 = naqs::deep_phase(net);
+        switch (d0.Ha >> 4) {
+#define NAQS_DEEP(C) case C:                                                                                                              \
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&agg_deep_backward_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024)); \
+            NAQS_KLAUNCH(agg_deep_backward_kernel<C>, dim3((unsigned)n_wg, (unsigned)d0.P, 2), dim3(naqs::DBW * WAVE), lds_d, s, d0, net->d_wdeep, da0, \
+                         const_cast<float *>(jobs[0].partial), d1, net->d_wph, da1, const_cast<float *>(jobs[1].partial), M, keys_dev, g_amp, g_ph, \
+                         g_stride, stride);                                                                                                \
+            break;
+            NAQS_DEEP(1) NAQS_DEEP(2) NAQS_DEEP(3) NAQS_DEEP(4) NAQS_DEEP(5) NAQS_DEEP(6) NAQS_DEEP(7) NAQS_DEEP(8)
+#undef NAQS_DEEP
+            default: return NAQS_ERR_UNSUPPORTED;
+        }
+        HIP_TRY(hipGetLastError());
+        std::snprintf(net->last_deep, sizeof(net->last_deep), "backward: agg_deep_backward_kernel<%d, L=%d>", d0.Ha >> 4, net->amp_depth);
+        return NAQS_OK;
+    }
     AmpSrc src0, src1;
     int st = net_blocks_backward_plan(net, d0, net->amp_src_off, net->amp_params, M, 0, &jobs[0], &src0);
     if (st != NAQS_OK) return st;

@@ -1004,6 +1004,79 @@ __global__ __launch_bounds__(DEEPK_WAVES * 64) void amp_deep_kernel(const NetDim
     }
 }
 
+// Aggregate phase with deep blocks (naqs_net_create_agg_layers): one (tile, pair) item of either set, amp_deep_kernel's arithmetic.
+// RAW (d = net->dph, the per-pair phase blocks): the realised outcome's output is the pair's phase, as amp_body's raw mode has it —
+// row phase_out_row(occ), and the last block's phase carries phase_sym_shift (nade.py:597-610, :758-759).
+template <int CT, bool RAW>
+__device__ __forceinline__ void amp_deep_body(const NetDims &d, const float *__restrict__ wdeep, const naqs::DeepAmp &da, const int64_t M,
+                                              const uint64_t *__restrict__ keys, float *__restrict__ scratch, const ElocFeed &feed,
+                                              const int n, const int64_t row0, float *outs, const int lane) {
+    const int64_t i = row0 + (lane & 15);
+    const uint64_t key = i < M ? keys[i] : 0ull;
+    uint32_t a = 0, b = 0;
+    naqs::key_strings(d, key, a, b);
+    naqs::amp_deep_item<CT, RAW>(d, wdeep + da.off[n], da.L, n, a | (b << 16), lane, outs);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (lane < 16 && i < M) {
+        float o[5];
+#pragma unroll
+        for (int c = 0; c < 5; ++c) o[c] = outs[lane * 8 + c];
+        const uint32_t mask = (1u << n) - 1u;
+        const int occ = (int)((a >> n) & 1u) + 2 * (int)((b >> n) & 1u);
+        if (RAW) {
+            const int row = naqs::phase_out_row(d, occ);
+            float ph = row == 0 ? o[0] : (row == 1 ? o[1] : (row == 2 ? o[2] : o[3]));
+            if (n == d.P - 1) ph += naqs::phase_sym_shift(d, a, b);          // (a, b: all P pairs)
+            scratch[(int64_t)n * M + i] = ph;
+        } else {
+            scratch[(int64_t)n * M + i] = naqs::amp_finish(d, n, o, a & mask, b & mask, occ);
+            if (n == 0 && feed.tab != nullptr) {
+                if (feed.key_bits == 32) naqs::feed_key<uint32_t>(feed, i, key);
+                else naqs::feed_key<uint64_t>(feed, i, key);
+            }
+        }
+    }
+}
+
+// aggregate phase with deep blocks: the phase blocks alone (raw; the amplitude set is amp_deep_kernel's) — the form for Ha != Hp
+template <int CT>
+__global__ __launch_bounds__(DEEPK_WAVES * 64) void amp_deep_raw_kernel(const NetDims d, const float *__restrict__ wdeep, const naqs::DeepAmp da,
+                                                                        const int64_t M, const uint64_t *__restrict__ keys,
+                                                                        float *__restrict__ scratch) {
+    __shared__ __attribute__((aligned(16))) float s_outs[DEEPK_WAVES][128];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t tiles = (M + 15) / 16;
+    const int64_t item = (int64_t)blockIdx.x * DEEPK_WAVES + wave;
+    if (item >= tiles * d.P) return;
+    const int n = (int)(item / tiles);
+    const int64_t row0 = (item - (int64_t)n * tiles) * 16;
+    const ElocFeed none{};
+    amp_deep_body<CT, true>(d, wdeep, da, M, keys, scratch, none, n, row0, s_outs[wave], lane);
+}
+
+// ... and both sets in ONE launch when Ha == Hp: items [0, tiles P) the amplitude blocks (conditionals, the E_loc feed), items
+// [tiles P, 2 tiles P) the phase blocks (raw) — the same items and arithmetic as the two launches, so the same bits
+template <int CT>
+__global__ __launch_bounds__(DEEPK_WAVES * 64) void agg_deep_kernel(const NetDims d0, const float *__restrict__ w0, const naqs::DeepAmp da0,
+                                                                    float *__restrict__ scratch0, const ElocFeed feed,
+                                                                    const NetDims d1, const float *__restrict__ w1, const naqs::DeepAmp da1,
+                                                                    float *__restrict__ scratch1, const int64_t M,
+                                                                    const uint64_t *__restrict__ keys) {
+    __shared__ __attribute__((aligned(16))) float s_outs[DEEPK_WAVES][128];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t tiles = (M + 15) / 16, set_items = tiles * d0.P;
+    int64_t item = (int64_t)blockIdx.x * DEEPK_WAVES + wave;
+    if (item >= 2 * set_items) return;                                           // wave-uniform; no barrier below
+    const bool phase = item >= set_items;
+    if (phase) item -= set_items;
+    const int n = (int)(item / tiles);
+    const int64_t row0 = (item - (int64_t)n * tiles) * 16;
+    if (!phase) amp_deep_body<CT, false>(d0, w0, da0, M, keys, scratch0, feed, n, row0, s_outs[wave], lane);
+    else { const ElocFeed none{}; amp_deep_body<CT, true>(d1, w1, da1, M, keys, scratch1, none, n, row0, s_outs[wave], lane); }
+}
+
 // the deep blocks' parameters from the flat state_dict vector into d_wdeep: pair blockIdx.y, moved to its 16-byte aligned offset
 __global__ __launch_bounds__(256) void deep_pack_kernel(const float *__restrict__ flat, const naqs::DeepAmp da, const int Ha, const int nout,
                                                         float *__restrict__ dst) {
@@ -2362,6 +2435,64 @@ NAQS_API int naqs_net_create_amp_layers(const naqs_net_config_t *cfg, int32_t n_
     return NAQS_OK;
 }
 
+NAQS_API int naqs_net_create_agg_layers(const naqs_net_config_t *cfg, int32_t n_hidden, int device, naqs_net_t **out) {
+    if (!cfg || !out) return NAQS_ERR_INVALID;
+    *out = nullptr;
+    if (n_hidden < 1 || n_hidden > naqs::MAX_AMP_LAYERS) return NAQS_ERR_INVALID;
+    if (cfg->aggregate_phase == 0) return NAQS_ERR_UNSUPPORTED;           // (the single-phase family: naqs_net_create_amp_layers)
+    if (n_hidden == 1) return naqs_net_create(cfg, device, out);
+    // every check that needs no device comes first
+    const int N = cfg->n_qubits;
+    if (N <= 0 || (N & 1)) return NAQS_ERR_INVALID;
+    if (N / 2 < 2 || N / 2 > MAXP) return NAQS_ERR_UNSUPPORTED;
+    if (cfg->n_phase_hidden != n_hidden) return NAQS_ERR_UNSUPPORTED;    // (mixed amplitude and phase depths: not this family)
+    const int Hp = cfg->phase_hidden[0];
+    for (int l = 1; l < n_hidden; ++l)
+        if (cfg->phase_hidden[l] != Hp) return NAQS_ERR_UNSUPPORTED;
+    if (Hp <= 0 || (Hp & 15) || Hp > 128) return NAQS_ERR_UNSUPPORTED;
+    if (cfg->amp_hidden > 0 && ((cfg->amp_hidden & 15) || cfg->amp_hidden > 128)) return NAQS_ERR_UNSUPPORTED;
+    // the depth-1 aggregate handle of the same widths, whose block sets are then re-described as deep ones
+    naqs_net_config_t c = *cfg;
+    c.n_phase_hidden = 1;
+    naqs_net_t *net = nullptr;
+    int st = naqs_net_create(&c, device, &net);
+    if (st != NAQS_OK) return st;
+    net->cfg = *cfg;
+    const NetDims &d = net->dims, &q = net->dph;
+    const int L = n_hidden;
+    int64_t off = 0, doff = 0;
+    for (int n = 0; n < d.P; ++n) {                       // amplitude blocks: exactly naqs_net_create_amp_layers' layout
+        const int64_t f = naqs::deep_pair_floats(d.Ha, d.n_out_amp, L, n);
+        net->amp_src_off[n] = off;
+        net->deep_off[n] = doff;
+        off += f;
+        doff += (f + 3) & ~3ll;
+    }
+    net->amp_params = off;
+    net->amp_depth = L;
+    net->deep_floats = doff;
+    int64_t poff = 0;
+    for (int n = 0; n < q.P; ++n) {                       // then the phase blocks, block by block
+        const int64_t f = naqs::deep_pair_floats(q.Ha, q.n_out_amp, L, n);
+        net->ph_src_off[n] = off;
+        net->ph_deep_off[n] = poff;
+        off += f;
+        poff += (f + 3) & ~3ll;
+    }
+    net->ph_params = off - net->amp_params;
+    net->n_params = off;
+    net->ph_deep_floats = poff;
+    DeviceGuard guard;
+    st = guard.init(device);
+    if (st == NAQS_OK && net->d_wamp) { (void)hipFree(net->d_wamp); net->d_wamp = nullptr; }     // (the depth-1 fragments: never read)
+    if (st == NAQS_OK && net->d_wph) { (void)hipFree(net->d_wph); net->d_wph = nullptr; }
+    if (st == NAQS_OK && hipMalloc((void **)&net->d_wdeep, (size_t)doff * sizeof(float)) != hipSuccess) st = NAQS_ERR_NOMEM;
+    if (st == NAQS_OK && hipMalloc((void **)&net->d_wph, (size_t)poff * sizeof(float)) != hipSuccess) st = NAQS_ERR_NOMEM;
+    if (st != NAQS_OK) { naqs_net_destroy(net); return st; }
+    *out = net;
+    return NAQS_OK;
+}
+
 NAQS_API int naqs_net_create_combined(const naqs_net_config_t *cfg, int device, naqs_net_t **out) {
     if (!cfg || !out) return NAQS_ERR_INVALID;
     *out = nullptr;
@@ -2458,6 +2589,16 @@ static int pack_deep(naqs_net *net, const float *flat_dev, hipStream_t s) {
     const int64_t biggest = naqs::deep_pair_floats(d.Ha, d.n_out_amp, net->amp_depth, d.P - 1);
     NAQS_KLAUNCH(deep_pack_kernel, dim3((unsigned)std::min<int64_t>(64, (biggest + 255) / 256), (unsigned)d.P), dim3(256), 0, s, flat_dev,
                        naqs::deep_amp(net), d.Ha, d.n_out_amp, net->d_wdeep);
+    HIP_TRY(hipGetLastError());
+    return NAQS_OK;
+}
+
+// ... and the deep phase blocks of an aggregate-phase handle (naqs_net_create_agg_layers) into d_wph, the same way
+static int pack_deep_phase(naqs_net *net, const float *flat_dev, hipStream_t s) {
+    const NetDims &q = net->dph;
+    const int64_t biggest = naqs::deep_pair_floats(q.Ha, q.n_out_amp, net->amp_depth, q.P - 1);
+    NAQS_KLAUNCH(deep_pack_kernel, dim3((unsigned)std::min<int64_t>(64, (biggest + 255) / 256), (unsigned)q.P), dim3(256), 0, s, flat_dev,
+                       naqs::deep_phase(net), q.Ha, q.n_out_amp, net->d_wph);
     HIP_TRY(hipGetLastError());
     return NAQS_OK;
 }
@@ -2730,6 +2871,14 @@ NAQS_API int naqs_net_set_weights(naqs_net_t *net, const float *flat_dev, int64_
     net->pack_pending_amp = false;
     if (net->overlap_next_pack != 2) net->amp_head_packed = 0;      // (only naqs_vmc_step's update packs leading pairs itself)
     if (net->comb) return pack_comb(net, flat_dev, s);      // (nothing is left pending: no launch hosts a share of it)
+    if (net->aggregate && net->amp_depth > 1) {             // deep blocks: both f32 copies, the amplitude set's first
+        st = pack_deep(net, flat_dev, s);
+        if (st != NAQS_OK) return st;
+        st = pack_deep_phase(net, flat_dev, s);
+        if (st != NAQS_OK) return st;
+        net->have_weights = net->have_amp_weights = net->have_wb = true;
+        return NAQS_OK;
+    }
     if (net->aggregate) {                                   // the phase blocks in the amplitude rows' layout; nothing else to pack
         if (net->dims.P == net->dph.P && (naqs::env_int("NAQS_AGG_MERGE", 7) & 4)) {
             AmpSrcOff so0, so1;
@@ -2812,6 +2961,51 @@ int naqs::net_amp_forward(naqs_net *net, int64_t M, const uint64_t *keys_dev, hi
     }
     std::snprintf(net->last_amp, sizeof(net->last_amp), "amp_kernel");
     return launch_amp_kernel(d, net->d_w, M, keys_dev, net->d_scratch, feed ? *feed : none, 0, s);
+}
+
+// aggregate_phase with deep blocks (naqs_net_create_agg_layers): both sets in agg_deep_kernel when Ha == Hp (NAQS_AGG_MERGE & 1),
+// else amp_deep_kernel (net_amp_forward, which also feeds E_loc the keys) and amp_deep_raw_kernel; then the sums
+static int agg_deep_logpsi(naqs_net *net, int64_t M, const uint64_t *keys_dev, float *logpsi_dev, hipStream_t s, const ElocFeed &feed) {
+    const NetDims &d0 = net->dims, &d1 = net->dph;
+    const bool prof = net->prof.armed();
+    if (prof) { int stp = net->prof.begin(s); if (stp != NAQS_OK) return stp; }
+    int st = naqs::net_amp_forward(net, M, keys_dev, s, nullptr, /*launch=*/false);          // (the scratch only)
+    if (st != NAQS_OK) return st;
+    float *s_ph = net->d_scratch + (size_t)d0.P * net->cap_M;
+    const naqs::DeepAmp da0 = naqs::deep_amp(net), da1 = naqs::deep_phase(net);
+    const int64_t set_items = (M + 15) / 16 * d0.P;
+    const int CT0 = d0.Ha >> 4, CT1 = d1.Ha >> 4;
+    if (CT0 < 1 || CT0 > 8 || CT1 < 1 || CT1 > 8 || d0.P != d1.P) return NAQS_ERR_UNSUPPORTED;
+    if (CT0 == CT1 && (naqs::env_int("NAQS_AGG_MERGE", 7) & 1)) {
+        const unsigned grid = (unsigned)((2 * set_items + DEEPK_WAVES - 1) / DEEPK_WAVES);
+        switch (CT0) {
+#define NAQS_DEEP(C) case C: NAQS_KLAUNCH(agg_deep_kernel<C>, dim3(grid), dim3(DEEPK_WAVES * 64), 0, s, d0, net->d_wdeep, da0, net->d_scratch, feed, \
+                                          d1, net->d_wph, da1, s_ph, M, keys_dev); break;
+            NAQS_DEEP(1) NAQS_DEEP(2) NAQS_DEEP(3) NAQS_DEEP(4) NAQS_DEEP(5) NAQS_DEEP(6) NAQS_DEEP(7) NAQS_DEEP(8)
+#undef NAQS_DEEP
+            default: return NAQS_ERR_UNSUPPORTED;
+        }
+        HIP_TRY(hipGetLastError());
+        std::snprintf(net->last_kernel, sizeof(net->last_kernel), "agg_deep_kernel<%d, L=%d> + agg_finish_kernel", CT0, net->amp_depth);
+    } else {
+        st = naqs::net_amp_forward(net, M, keys_dev, s, &feed);
+        if (st != NAQS_OK) return st;
+        const unsigned grid = (unsigned)((set_items + DEEPK_WAVES - 1) / DEEPK_WAVES);
+        switch (CT1) {
+#define NAQS_DEEP(C) case C: NAQS_KLAUNCH(amp_deep_raw_kernel<C>, dim3(grid), dim3(DEEPK_WAVES * 64), 0, s, d1, net->d_wph, da1, M, keys_dev, s_ph); break;
+            NAQS_DEEP(1) NAQS_DEEP(2) NAQS_DEEP(3) NAQS_DEEP(4) NAQS_DEEP(5) NAQS_DEEP(6) NAQS_DEEP(7) NAQS_DEEP(8)
+#undef NAQS_DEEP
+            default: return NAQS_ERR_UNSUPPORTED;
+        }
+        HIP_TRY(hipGetLastError());
+        std::snprintf(net->last_kernel, sizeof(net->last_kernel), "%s + amp_deep_raw_kernel<%d, L=%d> + agg_finish_kernel", net->last_amp, CT1,
+                      net->amp_depth);
+    }
+    NAQS_KLAUNCH(agg_finish_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, d0.P, M, net->d_scratch, s_ph,
+                       reinterpret_cast<float2 *>(logpsi_dev), feed);
+    HIP_TRY(hipGetLastError());
+    if (prof) { st = net->prof.end(s); if (st != NAQS_OK) return st; }
+    return NAQS_OK;
 }
 
 // aggregate_phase: amplitude blocks, phase blocks (raw), then the sums
@@ -2937,6 +3131,7 @@ int naqs::net_logpsi_impl(naqs_net *net, int64_t M, const uint64_t *keys_dev, fl
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     st = naqs::net_flush_pack(net, s);                     // (the phase share of the last step's re-pack, if no launch hosted it)
     if (st != NAQS_OK) return st;
+    if (net->aggregate && net->amp_depth > 1) return agg_deep_logpsi(net, M, keys_dev, logpsi_dev, s, feed);
     if (net->aggregate) return agg_logpsi(net, M, keys_dev, logpsi_dev, s, feed);
     if (net->comb) return comb_logpsi(net, M, keys_dev, logpsi_dev, s, feed);
     const int fmt = phase_format(d);

@@ -298,7 +298,12 @@ struct naqs_net {
     naqs::NetDims dph{};
     int64_t ph_src_off[naqs::MAXP] = {};          // per pair: offset of its phase block in the flat source
     int64_t ph_params = 0;
-    float *d_wph = nullptr;                 // packed phase blocks (layout of the amplitude rows)
+    float *d_wph = nullptr;                 // packed phase blocks (layout of the amplitude rows; deep phase blocks: naqs_amp_deep.hpp's)
+    // aggregate_phase with 2..4 hidden layers in every block (naqs_net_create_agg_layers): the amplitude set is exactly a
+    // naqs_net_create_amp_layers handle's (amp_depth, d_wdeep, deep_off); the phase blocks have the same depth and are packed
+    // into d_wph in the deep layout, pair n at ph_deep_off[n] (dph describes them: sym 0, 4 or 3 raw outputs)
+    int64_t ph_deep_off[naqs::MAXP] = {};
+    int64_t ph_deep_floats = 0;
     float *d_w = nullptr;                   // [amp params | packed phase layers]
     unsigned short *d_wh = nullptr;         // phase layers as 3 bf16 planes (phase_kernel_bf16x3)
     int64_t wh_elems = 0;

@@ -916,7 +916,8 @@ static int train_backward_impl(naqs_net_t *net, int64_t M, const uint64_t *keys_
     GradFinish F;
     if (net->aggregate) {
         // both sets of per-pair blocks through the same backward kernel: amplitude blocks on g[:, 0], phase blocks (raw
-        // outputs, no conditional) on g[:, 1]; the forward scratch ([2 P][cap] floats, free by now) holds the two columns
+        // outputs, no conditional) on g[:, 1]; the forward scratch ([2 P][cap] floats, free by now) holds the two columns.
+        // (deep blocks, naqs_net_create_agg_layers: the same two forms on the deep kernels — naqs_grad.hip)
         if (M > net->cap_M || !net->d_scratch) return NAQS_ERR_INVALID;
         if (net->dims.Ha == net->dph.Ha && net->dims.P == net->dph.P && (naqs::env_int("NAQS_AGG_MERGE", 7) & 2)) {
             // one launch for both sets, the two columns of g read where they are
@@ -1364,7 +1365,8 @@ NAQS_API int naqs_vmc_shard_sample_forward(naqs_net_t *net, int64_t n_samples, u
                                            void *stream) {
     if (!net || !info_host || !logpsi_shard_dev || world < 1 || rank < 0 || rank >= world) return NAQS_ERR_INVALID;
     info_host[2] = 0;
-    if (net->comb) return NAQS_ERR_UNSUPPORTED;           // (combined blocks: the replicated step only)
+    if (net->comb || (net->aggregate && net->amp_depth > 1)) return NAQS_ERR_UNSUPPORTED;     // (combined blocks, deep aggregate-phase
+                                                                                             //  blocks: the replicated step only)
     int64_t info2[2] = {0, 0};
     DeviceGuard guard;
     int st = guard.init(net->device);
@@ -1389,7 +1391,8 @@ NAQS_API int naqs_vmc_shard_update(naqs_net_t *net, const float *grad_dev, float
                                    double lr, double beta1, double beta2, double eps, double weight_decay, int64_t adam_step,
                                    void *stream) {
     if (!net || !grad_dev || !param_dev || !exp_avg_dev || !exp_avg_sq_dev || adam_step < 1) return NAQS_ERR_INVALID;
-    if (net->comb) return NAQS_ERR_UNSUPPORTED;           // (combined blocks: the replicated step only)
+    if (net->comb || (net->aggregate && net->amp_depth > 1)) return NAQS_ERR_UNSUPPORTED;     // (combined blocks, deep aggregate-phase
+                                                                                             //  blocks: the replicated step only)
     DeviceGuard guard;
     int st = guard.init(net->device);
     if (st != NAQS_OK) return st;

@@ -48,6 +48,7 @@ SIGNATURES = {
     "naqs_net_create": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.POINTER(c_vp)]),
     "naqs_net_create_amp_layers": (ctypes.c_int, [c_vp, ctypes.c_int32, ctypes.c_int, ctypes.POINTER(c_vp)]),
     "naqs_net_create_combined": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.POINTER(c_vp)]),
+    "naqs_net_create_agg_layers": (ctypes.c_int, [c_vp, ctypes.c_int32, ctypes.c_int, ctypes.POINTER(c_vp)]),
     "naqs_net_destroy": (ctypes.c_int, [c_vp]),
     "naqs_net_param_count": (ctypes.c_int, [c_vp, ctypes.POINTER(c_i64)]),
     "naqs_net_set_weights": (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp]),
@@ -92,7 +93,7 @@ SIGNATURES = {
 }
 
 NET_MAX_PAIRS, NET_MAX_PHASE_LAYERS = 16, 8
-NET_MAX_AMP_LAYERS = 4                 # hidden layers of an amplitude block (naqs_net_create_amp_layers)
+NET_MAX_AMP_LAYERS = 4                 # hidden layers of a block (naqs_net_create_amp_layers, naqs_net_create_agg_layers)
 
 
 class NetConfig(ctypes.Structure):

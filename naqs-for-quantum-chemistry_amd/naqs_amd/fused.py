@@ -6,12 +6,14 @@ Supported architecture families:
     <= 128 units), a single phase block (``aggregate_phase=False``) of 1..8 hidden layers <= 512 wide; with this single phase
     block the amplitude blocks may also have 2..4 hidden layers of one width (``-n_layer``; ``naqs_net_create_amp_layers``);
   * the reference's default ansatz (experiments/run.py:11-31): the same amplitude blocks and one phase block per orbital
-    pair (``aggregate_phase=True``), each with one hidden layer (multiple of 16, <= 128 units);
+    pair (``aggregate_phase=True``), each with one hidden layer (multiple of 16, <= 128 units); or every amplitude and phase
+    block with the same 2..4 hidden layers (``-n_layer``), one width per kind of block (``naqs_net_create_agg_layers``);
 both with or without the phase spin symmetry (``-phase_sym``, nade.py:281, 507-533, 590-610: spin-ordered inputs of the phase
 block(s), 3 outputs, the sign shift — since round 5);
   * combined amplitude-phase blocks with a single phase (``-single_phase -comb_amp_phase``, nade.py:294-303, 555-560): no phase
     MLP, the last one-hidden-layer amplitude block's output layer also carries the phase rows (``naqs_net_create_combined``);
-<= 16 orbital pairs.  Anything else (combined blocks with ``aggregate_phase=True`` or deeper blocks, look-up-table blocks) raises
+<= 16 orbital pairs.  Anything else (combined blocks with ``aggregate_phase=True`` or deeper blocks, amplitude and phase blocks of
+different depths with ``aggregate_phase=True``, look-up-table blocks) raises
 ``NotImplementedError`` — callers then stay on the PyTorch modules (same numbers, more launches), and ``wavefunction.fused()``
 says so on stdout.
 """
@@ -71,15 +73,17 @@ class FusedLogPsi:
         # -comb_amp_phase: the single-phase form with one hidden layer per block runs on the kernels (naqs_net_create_combined)
         self.comb = bool(getattr(m, "combined_amp_phase_blocks", False))
         amp_lin = m.amp_layers[0].linears()
-        # 1 hidden layer; or 2..4 of one width with a single phase block (naqs_net_create_amp_layers)
+        # 1 hidden layer; or 2..4 of one width with a single phase block (naqs_net_create_amp_layers), or with per-pair phase
+        # blocks of the same depth (naqs_net_create_agg_layers)
         self.amp_depth = len(amp_lin) - 1
         if self.comb and (self.aggregate or self.amp_depth != 1):
             raise NotImplementedError("fused log-psi: combined amplitude-phase blocks with aggregate_phase=True or more than one "
                                       "hidden layer (no published script uses them) run as PyTorch modules")
         if len(m.phase_layers) != (0 if self.comb else (m.P if self.aggregate else 1)):
             raise NotImplementedError("fused log-psi: unexpected number of phase blocks")
-        deep_ok = (not self.aggregate and 2 <= self.amp_depth <= _lib.NET_MAX_AMP_LAYERS
-                   and len({lin.out_features for lin in amp_lin[:-1]}) == 1)
+        ph_depth = len(m.phase_layers[0].linears()) - 1 if self.aggregate else 0
+        deep_ok = (2 <= self.amp_depth <= _lib.NET_MAX_AMP_LAYERS and len({lin.out_features for lin in amp_lin[:-1]}) == 1
+                   and (not self.aggregate or ph_depth == self.amp_depth))
         if self.amp_depth != 1 and not deep_ok:
             raise NotImplementedError("fused log-psi: amplitude blocks need exactly one hidden layer")
         ha = m.amp_layers[0].linears()[0].out_features
@@ -91,9 +95,10 @@ class FusedLogPsi:
         if self.comb:
             pass
         elif self.aggregate:
-            if len(hidden) != 1 or hidden[0] % 16 or hidden[0] > 128:
+            if len(hidden) != self.amp_depth or len(set(hidden)) != 1 or hidden[0] % 16 or hidden[0] > 128:
                 raise NotImplementedError("fused log-psi: aggregate_phase=True with other than one phase hidden layer per "
-                                          f"block of a multiple of 16, <= 128 units (got {hidden})")
+                                          f"block of a multiple of 16, <= 128 units (got {hidden}); deeper phase blocks need the "
+                                          "amplitude blocks' depth and one width")
         elif not 1 <= len(hidden) <= _lib.NET_MAX_PHASE_LAYERS or max(hidden) > 512:
             raise NotImplementedError("fused log-psi: 1..8 phase hidden layers of width <= 512")
         self._lib = _lib.load_library()
@@ -120,6 +125,9 @@ class FusedLogPsi:
         elif self.amp_depth == 1:
             st = self._lib.naqs_net_create(ctypes.byref(cfg), self.device.index or 0, ctypes.byref(self._h))
             _lib.check(st, "naqs_net_create")
+        elif self.aggregate:
+            st = self._lib.naqs_net_create_agg_layers(ctypes.byref(cfg), self.amp_depth, self.device.index or 0, ctypes.byref(self._h))
+            _lib.check(st, "naqs_net_create_agg_layers")
         else:
             st = self._lib.naqs_net_create_amp_layers(ctypes.byref(cfg), self.amp_depth, self.device.index or 0, ctypes.byref(self._h))
             _lib.check(st, "naqs_net_create_amp_layers")

@@ -280,6 +280,8 @@ class OptimizerBase:
             m = self.wavefunction.model
             if getattr(m, "combined_amp_phase_blocks", False) and not m.aggregate_phase:
                 mode = "replicated"          # -single_phase -comb_amp_phase: no sharded step (naqs_vmc_shard_* refuse its handles)
+            elif m.aggregate_phase and len(m.amp_layers[0].linears()) > 2:
+                mode = "replicated"          # aggregate phase with -n_layer >= 2: likewise (naqs_net_create_agg_layers' handles)
         if mode != self._dist_mode:
             if dist is not None:
                 self.dist_mode_log.append((self.n_steps, mode))
