@@ -471,20 +471,12 @@ typedef struct naqs_vmc_run_args {
     int64_t n_events, steps_done, last_keys_off;
     int32_t stop_reason, pad;
 } naqs_vmc_run_args_t;
-/* NAQS_DEFER_PHASE=1 (off by default: measured slower on this pool, the cross-stream hand-overs cost more than the overlap
- * wins): inside the run the phase MLP's half of a step — its share of the backward pass, its reductions + Adam update, its
- * re-pack — is issued on a second stream of the handle behind the amplitude blocks' half, so that it runs beside the NEXT
- * step's sampler (launches that read the amplitude blocks only and leave the chip almost empty) instead of in front of it;
- * the next forward pass waits for it, and so does this call before it returns: the caller never sees a half-updated
- * parameter vector.  Same kernels on the same operands either way. */
 int naqs_vmc_run(naqs_net_t *net, naqs_ham_t *ham, int64_t n_steps, naqs_vmc_run_args_t *args, void *stream);
 /* naqs_device_check for ONE network handle: its own wait-failure word only (what a caller that shares the device with other
  * runs asks; ABI 8). */
 int naqs_net_check(naqs_net_t *net);
-/* Order `stream` behind whatever work of this handle is still in flight on its own streams (the deferred phase chain of a
- * naqs_vmc_run that ended early with an error; a re-pack of the phase layers that no launch has hosted yet is started on
- * `stream`).  Every entry point that reads the phase layers does this itself; callers that read the flat parameter or
- * gradient buffers directly after such an error call it first.  No counterpart in the reference. */
+/* Start a re-pack of the weights that a training step left pending (one that no launch has hosted yet) on `stream`; nothing
+ * to do otherwise.  Every entry point that reads the packed weights does this itself.  No counterpart in the reference. */
 int naqs_net_finish_pending(naqs_net_t *net, void *stream);
 /* One Adam step on a flat float32 parameter vector (device pointers): torch.optim.Adam's rule without amsgrad —
  * the reference's optimiser, experiments/_base.py:228 (betas (0.9, 0.99), eps 1e-15).  `step` is the 1-based count

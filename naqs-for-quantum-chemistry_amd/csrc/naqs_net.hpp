@@ -321,8 +321,6 @@ struct naqs_net {
     int packed_fmt = 0;                     // split format of d_wh: 1 = three bf16 planes, 2 = two scaled f16 planes
     naqs::PhaseRaw *d_raw = nullptr;        // partial weight maxima of the phase layers (net_bounds_kernel -> pack_net_kernel)
     naqs::PhaseScales *d_scales = nullptr;  // the f16x2 scales of the current weights
-    unsigned short *d_wt = nullptr;            // the big layer's planes in phase_kernel_wt's order (W1's contraction index permuted per chunk)
-    bool have_wt = false;                      // ... packed from the current parameters (naqs_net_set_weights packs them; a training step's re-pack does not)
     unsigned long long *d_ws_xchg = nullptr;
     size_t ws_xchg_words = 0;   // phase_kernel_ws<.., SPLIT>: the producers' partial rows (tag << 32 | float), [cu_count / 2][64]
     uint32_t ws_seq = 0;                       // call tag of the last split launch (0 = no word written yet)
@@ -354,17 +352,7 @@ struct naqs_net {
     int64_t info_seq = 0;                   // sampling calls that published there
     naqs::PollHandle poll;                  // this handle's bounded-wait control block and error word (naqs_poll.hpp) ...
     const naqs::PollCtl *ctl = nullptr;     // ... = poll.dev: every kernel that polls gets it
-    hipStream_t side_stream = nullptr;      // NAQS_TRAIN_SIDE_STREAM=1: the amplitude blocks' backward beside the phase MLP's; naqs_vmc_run: the
-                                            // phase MLP's share of a step's backward pass, update and re-pack, beside the NEXT step's sampler
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    // naqs_vmc_run (round 5): the next sampler call reads the amplitude blocks only, and its three launches leave the chip
-    // almost empty for ~90 us — so the phase MLP's half of the backward pass, its reductions + Adam update and its re-pack
-    // run on side_stream behind the amplitude blocks' backward, and the caller's stream goes straight on to the sampler.
-    // Whoever needs the phase layers, the gradient or the parameters next waits for ev_phase_done first (net_flush_pack /
-    // naqs_net_finish_pending); naqs_vmc_run itself does before it returns, so its callers never see the pending state.
-    bool defer_phase = false;               // set by naqs_vmc_run around its steps (NAQS_DEFER_PHASE=0: never)
-    bool phase_pending = false;             // side_stream work the caller's stream has not been ordered behind yet
-    hipEvent_t ev_phase_done = nullptr;
+    hipEvent_t ev_fork = nullptr;           // pack_follow_update: orders a re-pack on another stream behind pack_stream
     hipStream_t pack_stream = nullptr;      // the stream whose work (the update) a pending re-pack must follow
     // naqs_vmc_step: the training forward launched ahead of the host's look at M (naqs::SpecRows)
     int64_t spec_hint = 0;                  // unique samples of the last accepted draw (0: none yet)
@@ -404,7 +392,7 @@ inline bool operator==(const PhaseForm &a, const PhaseForm &b) { return a.kind =
 // naqs_logpsi.hip: amp_kernel + phase kernel -> (log|psi|, phase)
 int net_logpsi_impl(naqs_net *net, int64_t M, const uint64_t *keys_dev, float *logpsi_dev, void *stream,
                     const ElocFeed &feed, const PhaseSave &save, const SpecRows *spec = nullptr);
-PhaseForm net_logpsi_form(const naqs_net *net, int64_t M, bool training);
+PhaseForm net_logpsi_form(const naqs_net *net, int64_t M);
 // naqs_phase_grad.hip: row-major padded copies of the phase weights for the backward GEMMs — described as jobs for the
 // one packing launch of naqs_net_set_weights (allocates the destination on first use)
 struct WbPackJobs {
@@ -414,9 +402,6 @@ struct WbPackJobs {
     float *dst[MAXL] = {};
 };
 int net_backward_pack_jobs(naqs_net *net, WbPackJobs *jobs);
-// naqs_logpsi.hip: order `s` behind whatever this handle still has in flight elsewhere (the deferred phase chain of
-// naqs_vmc_run), and start a pending re-pack of the phase layers on it
-int net_finish_pending(naqs_net *net, hipStream_t s);
 // naqs_logpsi.hip: the amplitude blocks' share of a training step's re-pack, if it is still waiting for a launch to host it
 // (naqs_pack.hpp) — for every reader of the amplitude rows / fragments that is not that launch
 int net_flush_amp_pack(naqs_net *net, hipStream_t s);

@@ -950,20 +950,7 @@ static int train_backward_impl(naqs_net_t *net, int64_t M, const uint64_t *keys_
     float *cpart = reinterpret_cast<float *>(base + L.cpart), *bpart = reinterpret_cast<float *>(base + L.bpart);
     const float2 *g2 = reinterpret_cast<const float2 *>(g_dev);
 
-    // amplitude blocks.  NAQS_TRAIN_SIDE_STREAM=1 runs them on a second stream beside the phase MLP's backward (independent:
-    // disjoint parts of the gradient, own scratch; 37 us and 59 us of latency-bound launches at M ~ 1 200).  Measured, three
-    // interleaved rounds on one box: N2 0.466 / 0.462 / 0.493 ms per step with it, 0.440 / 0.469 / 0.450 without; H2O 0.395 vs
-    // 0.387-0.399 — the fork / join events cost what the overlap wins, as they did for the forward pass in round 1.  Off.
-    const bool side = naqs::env_int("NAQS_TRAIN_SIDE_STREAM", 0) == 1;
-    hipStream_t sa = s;
-    if (side) {
-        if (!net->side_stream) HIP_TRY(hipStreamCreateWithFlags(&net->side_stream, hipStreamNonBlocking));
-        if (!net->ev_fork) HIP_TRY(hipEventCreateWithFlags(&net->ev_fork, hipEventDisableTiming));
-        if (!net->ev_join) HIP_TRY(hipEventCreateWithFlags(&net->ev_join, hipEventDisableTiming));
-        sa = net->side_stream;
-        HIP_TRY(hipEventRecord(net->ev_fork, s));                 // g (and the keys) are ready on the caller's stream
-        HIP_TRY(hipStreamWaitEvent(sa, net->ev_fork, 0));
-    }
+    // amplitude blocks
     const int H = d.n_lin - 1;
     const bool seed_delta = seeds != nullptr && H >= 1;   // the seeds and the last hidden layer's delta from one launch
     if (seed_delta) {
@@ -986,37 +973,24 @@ static int train_backward_impl(naqs_net_t *net, int64_t M, const uint64_t *keys_
                                nullptr, nullptr, 0u, nullptr);
         }
         HIP_TRY(hipGetLastError());
-        if (side) { HIP_TRY(hipEventRecord(net->ev_fork, s)); HIP_TRY(hipStreamWaitEvent(sa, net->ev_fork, 0)); }
     } else if (seeds != nullptr) {
-        // (on the caller's stream, before the fork: both halves of the backward pass read what it writes)
         NAQS_KLAUNCH(vmc_seed_kernel, dim3((unsigned)((M * L.top_ld + 255) / 256)), dim3(256), 0, s, d, M, keys_dev,
                            reinterpret_cast<const double2 *>(seeds->eloc), seeds->w, seeds->sums, reinterpret_cast<float2 *>(seeds->g_out),
                            g_amp, top, L.top_ld, seeds->ev);
         HIP_TRY(hipGetLastError());
-        if (side) { HIP_TRY(hipEventRecord(net->ev_fork, s)); HIP_TRY(hipStreamWaitEvent(sa, net->ev_fork, 0)); }
     } else {
-        NAQS_KLAUNCH(split_g_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, sa, M, g2, g_amp);
+        NAQS_KLAUNCH(split_g_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, M, g2, g_amp);
         HIP_TRY(hipGetLastError());
     }
     // NAQS_TRAIN_MEGA=0: every piece its own launch
-    const bool mega = H == 2 && d.Ha == 64 && net->amp_depth == 1 && !side && naqs::env_int("NAQS_TRAIN_MEGA", 1) == 1;
-    // naqs_vmc_run's steps: the phase MLP's half of what follows goes to the side stream (see the launch below)
-    const bool defer = net->defer_phase && mega && adam != nullptr && seed_delta;
-    hipStream_t sp = s;
-    if (defer) {
-        if (!net->side_stream) HIP_TRY(hipStreamCreateWithFlags(&net->side_stream, hipStreamNonBlocking));
-        if (!net->ev_fork) HIP_TRY(hipEventCreateWithFlags(&net->ev_fork, hipEventDisableTiming));
-        if (!net->ev_phase_done) HIP_TRY(hipEventCreateWithFlags(&net->ev_phase_done, hipEventDisableTiming));
-        sp = net->side_stream;
-    }
+    const bool mega = H == 2 && d.Ha == 64 && net->amp_depth == 1 && naqs::env_int("NAQS_TRAIN_MEGA", 1) == 1;
     naqs::ampbw::AmpSrc amp_src{};
     if (mega) st = naqs::net_blocks_backward_plan(net, net->dims, net->amp_src_off, net->amp_params, M, 0, &F.set[0], &amp_src);
-    else st = naqs::net_blocks_backward(net, net->dims, net->d_w, net->amp_src_off, net->amp_params, M, keys_dev, g_amp, grad_dev, 0, sa,
+    else st = naqs::net_blocks_backward(net, net->dims, net->d_w, net->amp_src_off, net->amp_params, M, keys_dev, g_amp, grad_dev, 0, s,
                                         &F.set[0], 0);
     if (st != NAQS_OK) return st;
     F.n_sets = 1;
     F.set_end[0] = net->amp_params;
-    if (side) HIP_TRY(hipEventRecord(net->ev_join, sa));
 
     // phase block.  First the chain of deltas, output layer down (the critical path: each needs the one above) ...
     if (seeds == nullptr) {
@@ -1094,44 +1068,18 @@ static int train_backward_impl(naqs_net_t *net, int64_t M, const uint64_t *keys_
         if (lds > 64 * 1024) return NAQS_ERR_UNSUPPORTED;
         A.fuse_w0 = w0_tiles && naqs::env_int("NAQS_FUSE_W0", 1) != 0 ? 1 : 0;
         A.w0 = W0Fuse{x, L.x_ld, cpart + J.cpart_off[0], bpart + J.bpart_off[0], J.Kp[0]};
-        if (defer) {
-            // naqs_vmc_run: the amplitude blocks' pieces alone on the caller's stream — the next sampler call needs nothing
-            // else — and the phase MLP's pieces (first hidden layer's delta, every layer's weight gradient) on the side
-            // stream BEHIND them, where they run beside that sampler call's almost empty launches instead of in front of them.
-            // Same device functions on the same operands: the same numbers as the one launch.
-            MegaArgs Aa = A;
-            Aa.n_gin = 0;
-            NAQS_KLAUNCH(backward_mega_kernel, dim3((unsigned)A.n_amp), dim3(256), lds, s, Aa, d, J, amp_src);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(net->ev_fork, s));
-            HIP_TRY(hipStreamWaitEvent(sp, net->ev_fork, 0));
-            MegaArgs Ap = A;
-            Ap.n_amp = 0;
-            NAQS_KLAUNCH(backward_mega_kernel, dim3((unsigned)(A.n_gin + blocks_total - J.block_end[0])), dim3(256), lds, sp, Ap, d, J, amp_src);
-            HIP_TRY(hipGetLastError());
-        } else {
-            NAQS_KLAUNCH(backward_mega_kernel, dim3((unsigned)(A.n_gin + A.n_amp + blocks_total - J.block_end[0])), dim3(256), lds, s,
-                               A, d, J, amp_src);
-            HIP_TRY(hipGetLastError());
-        }
+        NAQS_KLAUNCH(backward_mega_kernel, dim3((unsigned)(A.n_gin + A.n_amp + blocks_total - J.block_end[0])), dim3(256), lds, s,
+                           A, d, J, amp_src);
+        HIP_TRY(hipGetLastError());
         if (!A.fuse_w0) {
-            NAQS_KLAUNCH(grad_w_kernel, dim3((unsigned)J.block_end[0]), dim3(256), 0, sp, J, M, cpart, bpart, 0);
+            NAQS_KLAUNCH(grad_w_kernel, dim3((unsigned)J.block_end[0]), dim3(256), 0, s, J, M, cpart, bpart, 0);
             HIP_TRY(hipGetLastError());
         }
     } else {
         NAQS_KLAUNCH(grad_w_kernel, dim3((unsigned)blocks_total), dim3(256), 0, s, J, M, cpart, bpart, 0);
         HIP_TRY(hipGetLastError());
     }
-    if (side) HIP_TRY(hipStreamWaitEvent(s, net->ev_join, 0));   // the amplitude blocks' partial sums are complete
     F.total = F.set_end[0] + elems;
-    if (defer) {                                             // each half's reductions + Adam update behind its own pieces
-        st = launch_grad_finish(F, J, cpart, bpart, grad_dev, adam, s, 0, F.set_end[0]);
-        if (st != NAQS_OK) return st;
-        st = launch_grad_finish(F, J, cpart, bpart, grad_dev, adam, sp, F.set_end[0], F.total);
-        if (st != NAQS_OK) return st;
-        net->phase_pending = true;                           // (the re-pack and ev_phase_done follow: naqs_vmc_step)
-        return NAQS_OK;
-    }
     // naqs_vmc_step (NAQS_PACK_OVERLAP=2, the default): the launch's first workgroups each finish, update and PACK one of the
     // pairs the next sampler call's own first workgroup reads, so that the rest of the amplitude re-pack can ride in that call's
     // first launch (naqs_pack.hpp).  Conditions: what that launch needs to be the four-level head with the block MLPs on the matrix
@@ -1189,7 +1137,7 @@ NAQS_API int naqs_vmc_step(naqs_net_t *net, naqs_ham_t *ham, int64_t n_samples, 
             if (naqs::ham_device(ham) != net->device) return NAQS_OK;
             int64_t cover = std::min<int64_t>(max_unique, hint + std::max<int64_t>(64, hint / 8));
             if (naqs::env_int("NAQS_DEBUG_SPEC_SHRINK", 0) != 0) cover = std::max<int64_t>(16, hint / 2);      // (tests: a launch that does not fit)
-            form = naqs::net_logpsi_form(net, hint, /*training=*/true);
+            form = naqs::net_logpsi_form(net, hint);
             if (form.kind != 1) return NAQS_OK;
             int st = ensure_train_scratch(net, cover);
             if (st != NAQS_OK) return st;
@@ -1222,7 +1170,7 @@ NAQS_API int naqs_vmc_step(naqs_net_t *net, naqs_ham_t *ham, int64_t n_samples, 
     const int64_t M = info2[0];
     if (info2[1] != 0 || M <= 0 || M < m_lo || M > m_hi) return NAQS_OK;        // abandoned: the caller adapts n_samples
     net->spec_hint = M;
-    const bool spec_hit = specf.launched && M <= specf.rows && naqs::net_logpsi_form(net, M, true) == specf.form;
+    const bool spec_hit = specf.launched && M <= specf.rows && naqs::net_logpsi_form(net, M) == specf.form;
     if (spec_hit) ++net->spec_hits;
     // small tables: the weighted sums of E_loc are formed by the first workgroup of the backward pass's seed kernel (same
     // arithmetic, same order: naqs_reduce.hpp) instead of by a launch between E_loc and the seeds (NAQS_FUSE_SUMS=0: the launch)
@@ -1246,23 +1194,12 @@ NAQS_API int naqs_vmc_step(naqs_net_t *net, naqs_ham_t *ham, int64_t n_samples, 
         // fragments of the four pairs THAT workgroup reads were packed by the update's own launch, from the values it had just
         // written (grad_finish_kernel's first workgroups); naqs_pack.hpp.  NAQS_PACK_OVERLAP=1: round 4's form — the amplitude
         // jobs as a launch here, the phase layers' share hosted; 0: everything here, in order
-        const bool deferred = net->phase_pending;            // (train_backward_impl put the phase MLP's half on the side stream)
-        net->phase_pending = false;                          // (naqs_net_set_weights must not wait for what it is part of)
         const int overlap = naqs::env_int("NAQS_PACK_OVERLAP", 2);
         // (2 needs the update to have packed the leading pairs' fragments: train_backward_impl, net->amp_head_packed)
-        net->overlap_next_pack = deferred ? 1 : std::min(net->amp_head_packed > 0 ? 2 : 1, std::max(0, overlap));
+        net->overlap_next_pack = std::min(net->amp_head_packed > 0 ? 2 : 1, std::max(0, overlap));
         st = naqs_net_set_weights(net, param_dev, net->n_params, stream);
         net->overlap_next_pack = 0;
         if (st != NAQS_OK) return st;
-        if (deferred) {
-            // the phase layers' re-pack behind their update, on the side stream; whoever reads them, the gradient or the
-            // parameters next waits for ev_phase_done (net_flush_pack) — the next step's forward pass, ~100 us from here
-            net->pack_stream = net->side_stream;             // (nothing to order: the update ran on this very stream)
-            st = naqs::net_flush_pack(net, net->side_stream);
-            if (st != NAQS_OK) return st;
-            HIP_TRY(hipEventRecord(net->ev_phase_done, net->side_stream));
-            net->phase_pending = true;
-        }
     }
     info_host[2] = 1;
     return NAQS_OK;
@@ -1297,19 +1234,6 @@ NAQS_API int naqs_vmc_run(naqs_net_t *net, naqs_ham_t *ham, int64_t n_steps, naq
     a->last_keys_off = a->ring_elems > 0 ? a->ring_off : 0;
     const int64_t cap = a->n_unq_samples_max;
     const auto t0 = std::chrono::steady_clock::now();
-    // NAQS_DEFER_PHASE=1: the phase MLP's half of every step's backward pass / update / re-pack beside the next step's sampler
-    // (naqs_net.hpp); joined below, before the caller sees anything.  OFF by default — measured slower: the two event
-    // hand-overs between the streams cost 7-30 us of queue time per step on this pool where the split saves 2 (H2O) to 12 us
-    // (N2) of kernel time on the caller's stream: N2 0.188-0.190 ms per step against 0.185-0.187, H2O 0.142 against 0.130
-    // (profiles/r05_defer_phase_timeline.txt).  Same numbers either way (tests/test_optimizer_gpu.py).
-    struct DeferScope {
-        naqs_net_t *net; hipStream_t s;
-        ~DeferScope() {
-            net->defer_phase = false;
-            (void)naqs::net_finish_pending(net, s);
-        }
-    } scope{net, reinterpret_cast<hipStream_t>(stream)};
-    net->defer_phase = naqs::env_int("NAQS_DEFER_PHASE", 0) != 0;
     for (int64_t i = 0; i < n_steps; ++i) {
         if (a->ring_elems > 0 && a->ring_off + cap > a->ring_elems) { a->stop_reason = 1; break; }
         uint64_t *keys = a->keys_dev + (a->ring_elems > 0 ? a->ring_off : 0);

@@ -343,8 +343,6 @@ def _farm_launch(args, argv):
         mine = ",".join(str(j) for j in range(g, len(jobs), n_gpus))
         env = dict(os.environ, WORLD_SIZE=str(n_gpus), RANK=str(g), LOCAL_RANK=str(g), NAQS_FARM_DEVICE=str(g), NAQS_FARM_JOBS=mine)
         if args.per_gpu > 1:
-            # (NAQS_DEFER_PHASE=1 would give every replica a second stream of its own: a hardware queue too many — see below)
-            env["NAQS_DEFER_PHASE"] = "0"
             # the runs' sampler calls take turns on the device (include/naqs_hip.h: naqs_net_share_device): a
             # look-back launch is only certain to end while it is the one such launch in flight
             env.setdefault("NAQS_SHARED_GPU", "1")

@@ -222,7 +222,7 @@ def test_farm_launcher_tells_two_runs_per_gpu_to_share_the_device(monkeypatch, c
     monkeypatch.delenv("NAQS_SHARED_GPU", raising=False)
     ns = argparse.Namespace(molecule="LiH,H2O", seeds=None, seed=1, farm_gpus=1, per_gpu=2)
     _base._farm_launch(ns, ["-m", "LiH,H2O", "--farm", "--per-gpu", "2"])
-    assert seen[-1]["NAQS_SHARED_GPU"] == "1" and seen[-1]["NAQS_DEFER_PHASE"] == "0"
+    assert seen[-1]["NAQS_SHARED_GPU"] == "1"
     monkeypatch.setenv("NAQS_SHARED_GPU", "0")
     _base._farm_launch(ns, ["-m", "LiH,H2O", "--farm", "--per-gpu", "2"])
     assert seen[-1]["NAQS_SHARED_GPU"] == "0"
