@@ -150,6 +150,25 @@ int naqs_eloc_reduce(naqs_ham_t *h, int64_t n, const double *w_dev, const double
 int naqs_hmatvec(naqs_ham_t *h, int64_t M, const uint64_t *keys_dev, const double *v_dev, int64_t row_begin,
                  int64_t n_rows, double *out_dev, void *stream);
 
+/*
+ * The connected states of table rows [row_begin, row_begin + n_rows) that the table does not hold: what the reference's
+ * calculate_local_energy(set_unsampled_states_to_zero=False) would need psi for and never computes — its branch is
+ * `raise NotImplementedError()` above a commented-out sketch (src/optimizer/energy.py:227-235, 250-258).  The output is
+ * the set of keys j = key_i ^ xy_g over the rows i of the range and every non-diagonal XY group g of the handle
+ * (xy_g != 0) such that j passes the handle's particle-number filter (every j does when n_alpha = n_beta = -1) and j is
+ * not among the M keys; each j once, in any order; whether H_ij happens to sum to zero does not enter.
+ *
+ * out_keys_dev[capacity]  the set; *count_dev its size.  When the set is larger than `capacity` the call still
+ *                         returns NAQS_OK, with *count_dev > capacity (a lower bound of the size, not the size) and
+ *                         unspecified out_keys_dev contents; nothing is written past `capacity` and the call takes no
+ *                         longer than a successful one.  capacity = 0 (out_keys_dev may be null) asks "is the set empty".
+ * With E_loc over the table keys + set, rows [row_begin, row_begin + n_rows), this gives the local energy over ALL
+ * connected states.  The call rebuilds the handle's sample-key table (like naqs_eloc) and owns a scratch set of
+ * >= 2 capacity 64-bit slots that grows on demand.  n_qubits <= 63, capacity <= 2^30.
+ */
+int naqs_ham_connected(naqs_ham_t *h, int64_t M, const uint64_t *keys_dev, int64_t row_begin, int64_t n_rows,
+                       int64_t capacity, uint64_t *out_keys_dev, int64_t *count_dev, void *stream);
+
 /* ---- inner ring: device versions of the three Cython entry points the reference imports ---- */
 
 /* src.utils.hamiltonian_math.popcount_parity (hamiltonian_math.pyx:455-484):

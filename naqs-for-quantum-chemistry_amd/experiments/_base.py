@@ -68,6 +68,8 @@ _SWITCHES = [
     (("-single_phase",), "single_phase", lambda k: not k["aggregate_phase"], "Use only a single phase block."),
     (("-no_restrictedH",), "no_restrictedH", lambda k: not k["restrict_H"], "Do not restrict the ansatz to physical states."),
     (("-v", "--verbose"), "verbose", lambda k: k["verbose"], "Verbose logging."),
+    (("-exact_eloc",), "exact_eloc", lambda k: k["exact_eloc"],
+     "After training, estimate the energy from a fresh sample with exact local energies (psi on every connected state)."),
 ]
 _DEFAULTS = dict(molecule="molecules/H2", hamiltonian_fname=None, out=None, number=1, qubit_ordering=-1, lr=-1,
                  lr_lut=1e-2, n_samps=1e6, n_samps_max=1e12, n_unq_samps_min=50000, n_unq_samps_max=1e5,
@@ -76,7 +78,7 @@ _DEFAULTS = dict(molecule="molecules/H2", hamiltonian_fname=None, out=None, numb
                  load_hamiltonian=False, overwrite_hamiltonian=False, presolve_hamiltonian=False,
                  pretrained_model_loc=None, cont=False, n_excitations_max=-1, comb_amp_phase=False,
                  use_amp_spin_sym=True, use_phase_spin_sym=False, aggregate_phase=True, restrict_H=True,
-                 reset_opt=False, verbose=False, seed=-1)
+                 reset_opt=False, verbose=False, seed=-1, exact_eloc=False)
 
 
 def get_parser(**overrides):
@@ -173,7 +175,7 @@ def _run(molecule_fname, hamiltonian_fname, exp_name, num_experiments, pretraine
          reset_optimizer, qubit_ordering, masking, lr, lr_lut, n_samps, n_samps_max, n_unq_samps_min, n_unq_samps_max,
          reweight_samples_by_psi, n_train, n_pretrain, output_freq, save_freq, n_lut, n_hid, n_layer, n_hid_phase,
          n_layer_phase, n_excitations_max, comb_amp_phase, use_amp_spin_sym, use_phase_spin_sym, aggregate_phase,
-         use_restrictedH, loadH, presolveH, overwrite_pauli_hamiltonian, verbose, seed, device=None):
+         use_restrictedH, loadH, presolveH, overwrite_pauli_hamiltonian, verbose, seed, device=None, exact_eloc=False):
     # (-phase_sym runs on the HIP kernels since round 5, -comb_amp_phase with -single_phase and -n_layer 1 too (naqs_net_create_combined;
     # with the aggregate phase or deeper blocks as PyTorch modules on the device) — no published script uses either; -n_pretrain is
     # OptimizerBase.pre_flatten; -weight_by_psi is accepted and, as in the reference, has no effect on this optimiser:
@@ -192,7 +194,7 @@ def _run(molecule_fname, hamiltonian_fname, exp_name, num_experiments, pretraine
                            continue_experiment, reset_optimizer, qubit_ordering, masking, lr, lr_lut, n_samps, n_samps_max,
                            n_unq_samps_min, n_unq_samps_max, n_train, n_pretrain, output_freq, save_freq, n_lut, n_hid, n_layer,
                            n_hid_phase, n_layer_phase, comb_amp_phase, use_amp_spin_sym, use_phase_spin_sym, aggregate_phase,
-                           use_restrictedH, presolveH, verbose, seed, device)
+                           use_restrictedH, presolveH, verbose, seed, device, exact_eloc)
     finally:
         if locked[0]:
             _SETUP_LOCK.release()
@@ -204,7 +206,8 @@ _SETUP_LOCK = threading.RLock()
 def _run_locked(locked, molecule_fname, hamiltonian_fname, exp_name, num_experiments, pretrained_model_loc, continue_experiment,
                 reset_optimizer, qubit_ordering, masking, lr, lr_lut, n_samps, n_samps_max, n_unq_samps_min, n_unq_samps_max,
                 n_train, n_pretrain, output_freq, save_freq, n_lut, n_hid, n_layer, n_hid_phase, n_layer_phase, comb_amp_phase,
-                use_amp_spin_sym, use_phase_spin_sym, aggregate_phase, use_restrictedH, presolveH, verbose, seed, device):
+                use_amp_spin_sym, use_phase_spin_sym, aggregate_phase, use_restrictedH, presolveH, verbose, seed, device,
+                exact_eloc=False):
     seed = set_global_seed(_agree_on_seed(seed))
     molecule, qubit_hamiltonian = load_molecule(molecule_fname, hamiltonian_fname=hamiltonian_fname, verbose=True)
     N = molecule.n_qubits
@@ -292,11 +295,13 @@ def _run_locked(locked, molecule_fname, hamiltonian_fname, exp_name, num_experim
             opt.run(n_epochs=n_train // 2, save_freq=save_freq, save_final=True, output_freq=output_freq)
         train_time = time.time() - t0
         eig_val, _, n_unq = opt.solve_H(n_samps=opt.n_samples, ret_n_samps=True)
-        results.append(_summarise(opt, molecule, exp_name_i, eig_val, n_unq, train_time))
+        # -exact_eloc: the trained state's energy from a fresh draw with psi evaluated on every connected state
+        exact = opt.evaluate_energy(n_samps=opt.n_samples, exact=True) if exact_eloc else None
+        results.append(_summarise(opt, molecule, exp_name_i, eig_val, n_unq, train_time, exact=exact))
     return results
 
 
-def _summarise(opt, molecule, exp_name, eig_val, n_unq, train_time):
+def _summarise(opt, molecule, exp_name, eig_val, n_unq, train_time, exact=None):
     """summary.txt next to the checkpoints (the reference's _base.py:330-390, same quantities)."""
     e = np.array([x[1] for x in opt.log[LogKey.E_LOC]])
     window = min(50, len(e))
@@ -310,12 +315,17 @@ def _summarise(opt, molecule, exp_name, eig_val, n_unq, train_time):
     if fci is not None:
         lines.append(f"error to FCI (mHa) : {(final - fci) * 1e3:.4f}")
         lines.append(f"subspace-diag error to FCI (mHa) : {(eig_val - fci) * 1e3:.4f}")
+    res = dict(final=final, fci=fci, eig=eig_val, n_unq=n_unq, time=train_time)
+    if exact is not None:
+        lines.append(f"VMC energy with exact local energies: {exact['E']:.8f} ± {exact['stderr']:.2e} Ha "
+                     f"({exact['n_unq']} sampled + {exact['n_connected']} connected states)")
+        res.update(e_exact=exact["E"], e_exact_stderr=exact["stderr"])
     mk_dir(opt.save_loc, quiet=True)
     with open(os.path.join(opt.save_loc, "summary.txt"), "w") as f:
         f.write("\n".join(lines) + "\n")
     opt.save_log(quiet=True)
     print("\n".join(lines))
-    return dict(final=final, fci=fci, eig=eig_val, n_unq=n_unq, time=train_time)
+    return res
 
 
 def farm_jobs(molecules, seeds, seed):
@@ -441,6 +451,8 @@ def _run_job(args, molecule_fname, seed):
     masking = NadeMasking.NONE if args.no_mask_psi else (NadeMasking.FULL if args.full_mask_psi else NadeMasking.PARTIAL)
     print(f"Running experimental script: {__file__}\nResults will be saved to: {exp_name}/\n\nscript options:")
     for key, val in sorted(vars(args).items()):
+        if key == "exact_eloc" and not val:      # an opt-in of this port: without it the listing is the reference's
+            continue
         print(f"\t{key} : {val}")
     print("")
     return _run(molecule_fname=molecule_fname, hamiltonian_fname=args.hamiltonian_fname, exp_name=exp_name,
@@ -455,7 +467,7 @@ def _run_job(args, molecule_fname, seed):
                 comb_amp_phase=args.comb_amp_phase, use_amp_spin_sym=not args.no_amp_sym,
                 use_phase_spin_sym=args.phase_sym, aggregate_phase=not args.single_phase,
                 use_restrictedH=not args.no_restrictedH, loadH=args.loadH, presolveH=args.presolveH,
-                overwrite_pauli_hamiltonian=args.overwriteH, verbose=args.verbose, seed=seed)
+                overwrite_pauli_hamiltonian=args.overwriteH, verbose=args.verbose, seed=seed, exact_eloc=args.exact_eloc)
 
 
 def run(*args, **kwargs):

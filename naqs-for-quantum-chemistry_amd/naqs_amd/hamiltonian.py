@@ -120,6 +120,53 @@ class DevicePauliHamiltonian:
         _lib.check(st, "naqs_eloc_reduce")
         return out
 
+    # ---- connected states outside the table ----------------------------------------------------
+    def n_offdiagonal_groups(self):
+        return self.Kxy - (1 if self.diag_terms > 0 else 0)
+
+    def sector_size(self):
+        """Number of keys that pass the handle's particle-number filter (2^n without one)."""
+        p = self.packed
+        if p.n_alpha < 0:
+            return 1 << p.n_qubits
+        from math import comb
+        return comb((p.n_qubits + 1) // 2, p.n_alpha) * comb(p.n_qubits // 2, p.n_beta)
+
+    def connected_capacity(self, M, n_rows):
+        """A capacity that ``connected_keys`` cannot overflow for ``n_rows`` rows of a table of ``M``: the smaller of
+        rows x groups and what the sector has left (never more than the entry point's limit of 2^30)."""
+        return max(0, min(n_rows * self.n_offdiagonal_groups(), self.sector_size() - M, 1 << 30))
+
+    def connected_keys(self, keys, row_begin=0, n_rows=None, capacity=None):
+        """The connected states of table rows [row_begin, row_begin + n_rows) that are not among ``keys``
+        (``naqs_ham_connected``): key_i ^ xy_g over the rows and the non-diagonal groups, particle numbers conserved.
+
+        -> (int64 device tensor, sorted ascending — or None when the set is larger than ``capacity`` —, count).
+        On overflow ``count`` is only known to exceed ``capacity``.  The default capacity cannot overflow."""
+        M = keys.shape[0]
+        if n_rows is None:
+            n_rows = M - row_begin
+        if not (keys.is_cuda and keys.dtype == torch.int64):
+            raise ValueError("keys must be an int64 device tensor")
+        if row_begin < 0 or n_rows < 0 or row_begin + n_rows > M:
+            raise ValueError(f"rows [{row_begin}, {row_begin + n_rows}) are not rows of a table of {M}")
+        if capacity is None:
+            capacity = self.connected_capacity(M, n_rows)
+        capacity = int(capacity)
+        if n_rows == 0:
+            return torch.empty(0, dtype=torch.int64, device=self.device), 0
+        keys = keys.contiguous()
+        out = torch.empty(capacity, dtype=torch.int64, device=self.device)
+        count = torch.empty(1, dtype=torch.int64, device=self.device)
+        st = self._lib.naqs_ham_connected(self._h, M, keys.data_ptr(), int(row_begin), int(n_rows), capacity,
+                                          out.data_ptr() if capacity > 0 else None, count.data_ptr(), _stream_ptr(self.device))
+        _lib.check(st, "naqs_ham_connected")
+        n = int(count.item())
+        if n > capacity:
+            return None, n
+        # (bit patterns of uint64 keys: every supported key has bit 63 clear, so the signed order is the unsigned one)
+        return torch.sort(out[:n]).values, n
+
     # ---- H restricted to the sampled states, matrix-free ----------------------------------------
     def matvec(self, keys, v, out=None):
         """out_i = sum_j H_ij v_j over the sampled keys (``naqs_hmatvec``).  v: real [M] or complex-as-pairs [M, 2]

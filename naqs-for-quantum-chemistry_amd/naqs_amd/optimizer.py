@@ -398,13 +398,20 @@ class OptimizerBase:
     # ---- the hot path ----
     @torch.no_grad()
     def calculate_local_energy(self, states_idx, psi=None, set_unsampled_states_to_zero=True, ret_complex=False,
-                               log_psi=None, row_begin=0, n_rows=None):
+                               log_psi=None, row_begin=0, n_rows=None, psi_fn=None, max_table=2 ** 22):
         """E_loc of the sampled states (energy.py:219-263).  ``psi``: [M, 2] (Re, Im) like the
         reference, or pass ``log_psi`` [M, 2] = (log|psi|, phase) directly (better conditioned).
-        Un-sampled connected states contribute zero — the only mode the reference implements.
+        With ``set_unsampled_states_to_zero`` (the default, and the only mode the reference implements) un-sampled
+        connected states contribute zero.  Without it psi is evaluated on every connected state outside the table
+        (``_exact_local_energy``; ``psi_fn`` and ``max_table`` belong to that mode): the sum runs over all s'.
         Returns a float64 device tensor [n_rows, 2], or a complex128 numpy array with ret_complex."""
         if not set_unsampled_states_to_zero:
-            raise NotImplementedError()
+            e = self._exact_local_energy(keys_to_device(states_idx, self.device), psi=psi, log_psi=log_psi, row_begin=row_begin,
+                                         n_rows=n_rows, psi_fn=psi_fn, max_table=max_table)[0]
+            if ret_complex:
+                v = e.cpu().numpy()
+                return v[:, 0] + 1j * v[:, 1]
+            return e
         keys = keys_to_device(states_idx, self.device)
         if psi is None and log_psi is None:
             log_psi = self.wavefunction.log_psi(self.hilbert.idx2state(keys))
@@ -419,6 +426,110 @@ class OptimizerBase:
             v = e.cpu().numpy()
             return v[:, 0] + 1j * v[:, 1]
         return e
+
+    def _log_psi_of_keys(self, keys, psi_fn=None):
+        """(log|psi|, phase) float64 [n, 2] on the device for arbitrary keys: ``psi_fn`` when given, else the HIP forward
+        kernels, else — networks on the announced fallback — the PyTorch modules."""
+        if psi_fn is not None:
+            lp = psi_fn(keys)
+        else:
+            fused = self.wavefunction.fused(need_phase=True) if self.use_fused else None
+            if fused is not None:
+                lp = fused.log_psi(keys)
+            else:
+                lp = self.wavefunction.log_psi(self.hilbert.idx2state(keys))
+        return torch.as_tensor(lp).detach().reshape(-1, 2).to(self.device, torch.float64)
+
+    @torch.no_grad()
+    def _exact_local_energy(self, keys, psi=None, log_psi=None, row_begin=0, n_rows=None, psi_fn=None, max_table=2 ** 22,
+                            weights=None):
+        """E_loc(s) = sum_{s'} H_{s s'} psi(s') / psi(s) over ALL connected s' — the branch the reference leaves as
+        ``raise NotImplementedError()`` (energy.py:227-235, 250-258).  The rows are walked in blocks: the connected
+        states of the block that the table lacks (``naqs_ham_connected``), psi there, and the ordinary E_loc kernel on
+        table + connected states for the block's rows — for those rows nothing is missing from that table.  A block whose
+        table would exceed ``max_table`` rows is halved and tried again (an overflowing ``connected_keys`` call is a
+        count, nothing more).  -> (E_loc float64 [n_rows, 2], weighted sums [4] of ``weights`` [n_rows] or None,
+        number of states outside the table psi was evaluated on, a state reached from two blocks counting twice)."""
+        from ._lib import NaqsError
+        if self.bug_compat_full_sample_order:
+            raise NotImplementedError("exact local energies with bug_compat_full_sample_order: the quirk reorders the table")
+        ham = self.pauli_hamiltonian
+        M = keys.shape[0]
+        if n_rows is None:
+            n_rows = M - row_begin
+        if psi is not None and log_psi is None:
+            # the caller's (Re, Im) of the sampled rows as they are; the new states' values are converted to match
+            kind, wf = "psi", psi.detach().reshape(-1, 2).to(self.device, torch.float64)
+        else:
+            kind = "log_psi"
+            wf = (self._log_psi_of_keys(keys, psi_fn) if log_psi is None
+                  else log_psi.detach().reshape(-1, 2).to(self.device, torch.float64))
+        if wf.shape[0] != M:
+            raise ValueError(f"wave function must have shape [{M}, 2], got {tuple(wf.shape)}")
+        out = torch.empty((n_rows, 2), dtype=torch.float64, device=self.device)
+        sums = torch.zeros(4, dtype=torch.float64, device=self.device) if weights is not None else None
+        if weights is not None:
+            weights = weights.reshape(-1).to(self.device, torch.float64)
+        room = int(max_table) - M
+        if room < 0 and n_rows > 0:
+            raise NaqsError(f"the table of {M} sampled states alone exceeds max_table = {int(max_table)}")
+        b, end, step, n_conn = row_begin, row_begin + n_rows, n_rows, 0
+        while b < end:
+            n = min(step, end - b)
+            conn, count = ham.connected_keys(keys, b, n, capacity=min(room, ham.connected_capacity(M, n)))
+            if conn is None:
+                if n == 1:
+                    raise NaqsError(f"row {b}: more than {room} connected states outside the table of {M} "
+                                    f"(at least {count}); max_table = {int(max_table)} cannot hold them")
+                step = (n + 1) // 2
+                continue
+            if count:
+                lp_new = self._log_psi_of_keys(conn, psi_fn)
+                if kind == "psi":
+                    amp = lp_new[:, 0].exp()
+                    lp_new = torch.stack([amp * lp_new[:, 1].cos(), amp * lp_new[:, 1].sin()], -1)
+                t_keys, t_wf = torch.cat([keys, conn]), torch.cat([wf, lp_new])
+            else:
+                t_keys, t_wf = keys, wf
+            o = out[b - row_begin:b - row_begin + n]
+            if weights is not None:
+                sums += ham.local_energy(t_keys, t_wf, kind=kind, row_begin=b, n_rows=n, out=o,
+                                         weights=weights[b - row_begin:b - row_begin + n])[1]
+            else:
+                ham.local_energy(t_keys, t_wf, kind=kind, row_begin=b, n_rows=n, out=o)
+            n_conn += count
+            b += n
+        return out, sums, n_conn
+
+    @torch.no_grad()
+    def evaluate_energy(self, n_samps=None, keys=None, weights=None, exact=True, psi_fn=None, max_table=2 ** 22):
+        """The VMC estimate of <psi|H|psi> / <psi|psi> from a sample table, with exact local energies (``exact``: psi
+        evaluated on every connected state, so the weighted mean is unbiased and its variance vanishes at an eigenstate)
+        or with the truncated ones the training step uses.  The table is a fresh draw of ``n_samps`` (default: the
+        optimiser's sample count) from the run's own sampler, or the given ``keys`` with ``weights``.
+        -> {"E", "Var", "stderr", "n_unq", "n_connected"}; ``stderr`` = sqrt(Var / n_samps) for a drawn table, else None.
+        Reads the parameters; changes neither them nor the optimiser."""
+        drawn = keys is None
+        if drawn:
+            if n_samps is None:
+                n_samps = int(self.get_n_samples())
+            _, counts, _, keys, weights = self.wavefunction.sample(
+                int(n_samps), ret_log_psi=False, max_batch_size=getattr(self, "n_unq_samples_max", None),
+                generator=self.generator, ret_keys=True, ret_weights=True)
+        elif weights is None:
+            raise ValueError("evaluate_energy(keys=...) needs the weights of those states")
+        keys = keys_to_device(keys, self.device)
+        w = torch.as_tensor(weights).reshape(-1).to(self.device, torch.float64)
+        if exact:
+            _, sums, n_conn = self._exact_local_energy(keys, psi_fn=psi_fn, max_table=max_table, weights=w)
+        else:
+            _, sums = self.pauli_hamiltonian.local_energy(keys, self._log_psi_of_keys(keys, psi_fn), kind="log_psi", weights=w)
+            n_conn = 0
+        s = sums.tolist()
+        energy = s[0] / s[3]
+        var = s[2] / s[3] - energy * energy
+        stderr = math.sqrt(max(var, 0.0) / float(n_samps)) if drawn else None
+        return {"E": energy, "Var": var, "stderr": stderr, "n_unq": int(keys.shape[0]), "n_connected": int(n_conn)}
 
     @torch.no_grad()
     def calculate_energy(self, normalise_psi=None):
