@@ -42,7 +42,7 @@ __device__ __forceinline__ void amp_backward_pair(const NetDims &d, const float 
                                                   float *__restrict__ out, float *smem, const int raw, const int wg,
                                                   const int n_wgs, const int g_stride) {
     constexpr int NIN = NB == 0 ? 1 : 2 * NB;
-    constexpr int S = (NIN + 1 + 5 + 3) & ~3;
+    constexpr int S = amp_row_stride(NIN);
     constexpr int RT = (NIN + 1 + 15) / 16;               // 16-row tiles of the input axis (inputs + the bias input)
     constexpr int LD = GT + 1;
     const int Ha = d.Ha, nout = d.n_out_amp, NW = Ha >> 4, NT = NW * WAVE;
@@ -214,7 +214,7 @@ __device__ __forceinline__ void amp_backward_pair(const NetDims &d, const float 
 // floats of LDS one workgroup needs (any pair of the network)
 inline size_t smem_floats(const NetDims &d) {
     const int nin_max = 2 * (d.P - 1);
-    const int S_max = (nin_max + 1 + 5 + 3) & ~3;
+    const int S_max = amp_row_stride(nin_max);
     const int NW = d.Ha >> 4;
     return (size_t)((d.Ha * S_max + 8 + 3) & ~3) + 2 * (size_t)d.Ha * (GT + 1) + 5 * GT + GT + (size_t)NW * 5 * GT;
 }

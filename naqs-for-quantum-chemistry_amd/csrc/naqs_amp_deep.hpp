@@ -1,4 +1,4 @@
-// naqs_amp_deep.hpp — amplitude blocks with 2..4 hidden layers of one width Ha (naqs_net_create_amp_layers): the weight
+// naqs_amp_deep.hpp — amplitude blocks with 2..4 hidden layers of one width Ha (BlockSet::depth > 1): the weight
 // layout, the forward evaluator for one (tile of 16 samples, pair) work item and the backward pass for one pair, shared by
 // the standalone log-amplitude launch (naqs_logpsi.hip: amp_deep_kernel), the tree sampler (naqs_sample.hip:
 // sample_expand_deep_kernel) and the gradient (naqs_grad.hip: amp_deep_backward_kernel).  gfx950 only.
@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "naqs_net.hpp"
 
@@ -43,19 +44,29 @@ struct DeepAmp {
     int64_t src[MAXP] = {};       // ... and in the flat source
 };
 
-// the handle's description of its deep blocks (kernel argument)
-inline DeepAmp deep_amp(const naqs_net *net) {
+// a deep block set's description of itself (kernel argument)
+inline DeepAmp deep_blocks(const BlockSet &b) {
     DeepAmp a;
-    a.L = net->amp_depth;
-    for (int n = 0; n < MAXP; ++n) { a.off[n] = net->deep_off[n]; a.src[n] = net->amp_src_off[n]; }
+    a.L = b.depth;
+    for (int n = 0; n < MAXP; ++n) { a.off[n] = b.deep_off[n]; a.src[n] = b.src_off[n]; }
     return a;
 }
-// ... and of its deep phase blocks (naqs_net_create_agg_layers: the same depth, packed into d_wph)
-inline DeepAmp deep_phase(const naqs_net *net) {
-    DeepAmp a;
-    a.L = net->amp_depth;
-    for (int n = 0; n < MAXP; ++n) { a.off[n] = net->ph_deep_off[n]; a.src[n] = net->ph_src_off[n]; }
-    return a;
+
+// The deep kernels are templates on CT = Ha / 16 in 1..8: f(std::integral_constant<int, CT>) for the runtime width, which launches
+// and returns a status; any other width: NAQS_ERR_UNSUPPORTED, f not called.
+template <typename F>
+inline int dispatch_width(const int ct, F &&f) {
+    switch (ct) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 5: return f(std::integral_constant<int, 5>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        case 7: return f(std::integral_constant<int, 7>{});
+        case 8: return f(std::integral_constant<int, 8>{});
+        default: return NAQS_ERR_UNSUPPORTED;
+    }
 }
 
 #if defined(__HIPCC__)
@@ -130,7 +141,7 @@ __device__ __forceinline__ void deep_dense(const float *__restrict__ wl, int row
 // One wave, one (tile of 16 samples, pair n) item through all L hidden layers: the block's raw outputs -> outs[sample][8]
 // (entries >= nout are 0).  ab: the occupation strings (alpha | beta << 16) of sample lane & 15.  wp: pair n's packed block.
 // hs (optional): per hidden layer l the post-ReLU activations, hs[l - 1][unit * hs_ld + sample] (the backward pass).
-// RAW: a phase block of an aggregate-phase network (d = net->dph): it orders its inputs under d.phase_sym, not d.sym.
+// RAW: a phase block of an aggregate-phase network (d = net->ph.d): it orders its inputs under d.phase_sym, not d.sym.
 template <int CT, bool RAW = false>
 __device__ __forceinline__ void amp_deep_item(const NetDims &d, const float *__restrict__ wp, int L, int n, uint32_t ab, int lane,
                                               float *__restrict__ outs, float *hs = nullptr, int hs_ld = 0, int hs_layer = 0) {
@@ -201,7 +212,7 @@ __device__ __forceinline__ void deep_gemm(int J, int K, FA fa, FB fb, float *__r
     }
 }
 
-// RAW: a phase block of an aggregate-phase network (d = net->dph): d out[c] = g_i [c == phase_out_row(occ)], no conditional, and
+// RAW: a phase block of an aggregate-phase network (d = net->ph.d): d out[c] = g_i [c == phase_out_row(occ)], no conditional, and
 // the inputs in phase_sym order (the depth-1 blocks' raw mode, naqs_amp_backward.hpp).  g_stride 2: a column of the loss gradient [M][2].
 template <int CT, bool RAW = false>
 __device__ __forceinline__ void amp_deep_backward_pair(const NetDims &d, const float *__restrict__ wp, const int L, const int n,

@@ -68,6 +68,7 @@ __device__ __forceinline__ int exp_of(float x) { return (int)((__float_as_uint(x
 // Fragments per pair (pack_amp_mfma_body): W1 planes [2][Ha/16][64 lanes][8], W2 planes [2][Ha/32][64 lanes][8] (f16), then
 // 16 floats: b2[0..8), c1 = s_h / s_w1 (layer-1 accumulator -> scaled activation), c2 = 1 / (s_h s_w2).
 // ------------------------------------------------------------------------------------------------
+// (two planes of amp_frag_plane_elems(Ha) elements + 32, spelled out in 64 bits: the kernels' address arithmetic)
 __device__ __host__ __forceinline__ size_t amp_mfma_pair_elems(int Ha) { return (size_t)2 * 512 * ((Ha >> 4) + (Ha >> 5)) + 32; }
 
 // registers of one (tile, pair) work item: every global load is issued up front, one item ahead of its use

@@ -69,7 +69,7 @@ __global__ __launch_bounds__(naqs::DBW * 64) void amp_deep_backward_kernel(const
     naqs::amp_deep_backward_pair<CT>(d, wdeep + da.off[n], da.L, n, M, keys, g, out, smem, (int)blockIdx.x, (int)gridDim.x);
 }
 
-// aggregate phase with deep blocks (naqs_net_create_agg_layers): the phase blocks (raw, d = net->dph) on g with stride g_stride, the
+// aggregate phase with deep blocks (naqs_net_create_agg_layers): the phase blocks (raw, d = net->ph.d) on g with stride g_stride, the
 // same partial-sum layout
 template <int CT>
 __global__ __launch_bounds__(naqs::DBW * 64) void amp_deep_backward_raw_kernel(const NetDims d, const float *__restrict__ wdeep,
@@ -237,9 +237,9 @@ NAQS_API int naqs_net_phase_inputs(naqs_net_t *net, int64_t M, const uint64_t *k
     DeviceGuard guard;
     int st = guard.init(net->device);
     if (st != NAQS_OK) return st;
-    const int64_t total = M * 2 * (net->dims.P - 1);
+    const int64_t total = M * 2 * (net->amp.d.P - 1);
     NAQS_KLAUNCH(phase_inputs_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                       net->dims, M, keys_dev, x_dev, occ_dev);
+                       net->amp.d, M, keys_dev, x_dev, occ_dev);
     HIP_TRY(hipGetLastError());
     return NAQS_OK;
 }
@@ -296,7 +296,7 @@ NAQS_API int naqs_shard_proof(int64_t M, const uint64_t *keys_dev, const double 
 
 NAQS_API int naqs_net_amp_param_count(const naqs_net_t *net, int64_t *count) {
     if (!net || !count) return NAQS_ERR_INVALID;
-    *count = net->amp_params;
+    *count = net->amp.n_params;
     return NAQS_OK;
 }
 
@@ -312,63 +312,60 @@ NAQS_API int naqs_net_logamp(naqs_net_t *net, int64_t M, const uint64_t *keys_de
     if (st != NAQS_OK) return st;
     st = naqs::net_amp_forward(net, M, keys_dev, s);
     if (st != NAQS_OK) return st;
-    NAQS_KLAUNCH(logamp_sum_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, net->dims.P, M, net->d_scratch,
+    NAQS_KLAUNCH(logamp_sum_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, net->amp.d.P, M, net->d_scratch,
                        logamp_dev);
     HIP_TRY(hipGetLastError());
     return NAQS_OK;
 }
 
-// gradient of sum_i g_i f(key_i) for one set of per-pair blocks (amplitude blocks: f = log|psi|; raw: the phase blocks
+// the two halves of the partial-sum scratch, one per block set that may be pending (allocated on first use): `slot`'s half
+static int blocks_partials(naqs_net *net, const int slot, int64_t *stride, float **gpart) {
+    *stride = (std::max(net->amp.n_params, net->ph.n_params) + 3) & ~3ll;
+    if (!net->d_gpart) HIP_TRY(hipMalloc((void **)&net->d_gpart, 2 * (size_t)MAX_TILE_WGS * *stride * sizeof(float)));
+    *gpart = net->d_gpart + (slot ? (size_t)MAX_TILE_WGS * *stride : 0);
+    return NAQS_OK;
+}
+
+// gradient of sum_i g_i f(key_i) for one set of per-pair blocks (amplitude blocks: f = log|psi|; a raw set: the phase blocks
 // of an aggregate-phase network, f = phase): partial sums per workgroup, then a fixed-order reduction
-int naqs::net_blocks_backward(naqs_net *net, const NetDims &d, const float *w, const int64_t *src_off, int64_t n_block_params,
-                              int64_t M, const uint64_t *keys_dev, const float *g_dev, float *grad_dev, int raw, hipStream_t s,
-                              BlockReduceJob *defer, int slot) {
+int naqs::net_blocks_backward(naqs_net *net, const BlockSet &set, int64_t M, const uint64_t *keys_dev, const float *g_dev, float *grad_dev,
+                              hipStream_t s, BlockReduceJob *defer, int slot) {
+    const NetDims &d = set.d;
     if (d.Ha > 128 || (d.Ha & 15)) return NAQS_ERR_UNSUPPORTED;                 // a wave owns 16-unit hidden tiles
     if (M == 0) {
         if (defer) return NAQS_ERR_INVALID;
-        HIP_TRY(hipMemsetAsync(grad_dev, 0, (size_t)n_block_params * sizeof(float), s));
+        HIP_TRY(hipMemsetAsync(grad_dev, 0, (size_t)set.n_params * sizeof(float), s));
         return NAQS_OK;
     }
     const int n_wg = (int)std::min<int64_t>(MAX_TILE_WGS, (M + GT - 1) / GT);
-    const int64_t stride = (std::max(net->amp_params, net->ph_params) + 3) & ~3ll;
-    if (!net->d_gpart) {
-        HIP_TRY(hipMalloc((void **)&net->d_gpart, 2 * (size_t)MAX_TILE_WGS * stride * sizeof(float)));
-    }
-    float *gpart = net->d_gpart + (slot ? (size_t)MAX_TILE_WGS * stride : 0);
-    if (net->amp_depth > 1 && raw == 0 && &d == &net->dims) {       // deep amplitude blocks
-        const size_t lds_d = naqs::deep_bw_smem_floats(d.Ha, net->amp_depth) * sizeof(float);
+    int64_t stride;
+    float *gpart;
+    int st = blocks_partials(net, slot, &stride, &gpart);
+    if (st != NAQS_OK) return st;
+    if (set.deep()) {
+        const size_t lds_d = naqs::deep_bw_smem_floats(d.Ha, set.depth) * sizeof(float);
         if (lds_d > 156 * 1024) return NAQS_ERR_UNSUPPORTED;
-        const naqs::DeepAmp da = naqs::deep_amp(net);
-        switch (d.Ha >> 4) {
-#define NAQS_DEEP(C) case C:                                                                                                              \
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&amp_deep_backward_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024)); \
-            NAQS_KLAUNCH(amp_deep_backward_kernel<C>, dim3((unsigned)n_wg, (unsigned)d.P), dim3(naqs::DBW * WAVE), lds_d, s, d, net->d_wdeep, da, M, \
-                         keys_dev, g_dev, gpart, stride);                                                                                 \
-            break;
-            NAQS_DEEP(1) NAQS_DEEP(2) NAQS_DEEP(3) NAQS_DEEP(4) NAQS_DEEP(5) NAQS_DEEP(6) NAQS_DEEP(7) NAQS_DEEP(8)
-#undef NAQS_DEEP
-            default: return NAQS_ERR_UNSUPPORTED;
-        }
-        HIP_TRY(hipGetLastError());
-        std::snprintf(net->last_deep, sizeof(net->last_deep), "backward: amp_deep_backward_kernel<%d, L=%d>", d.Ha >> 4,
-                      net->amp_depth);
-    } else if (net->amp_depth > 1 && raw == 1 && net->aggregate && &d == &net->dph) {      // deep phase blocks (naqs_net_create_agg_layers)
-        const size_t lds_d = naqs::deep_bw_smem_floats(d.Ha, net->amp_depth) * sizeof(float);
-        if (lds_d > 156 * 1024) return NAQS_ERR_UNSUPPORTED;
-        const naqs::DeepAmp da = naqs::deep_phase(net);
-        switch (d.Ha >> 4) {
-#define NAQS_DEEP(C) case C:                                                                                                              \
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&amp_deep_backward_raw_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024)); \
-            NAQS_KLAUNCH(amp_deep_backward_raw_kernel<C>, dim3((unsigned)n_wg, (unsigned)d.P), dim3(naqs::DBW * WAVE), lds_d, s, d, net->d_wph, da, M, \
-                         keys_dev, g_dev, 1, gpart, stride);                                                                              \
-            break;
-            NAQS_DEEP(1) NAQS_DEEP(2) NAQS_DEEP(3) NAQS_DEEP(4) NAQS_DEEP(5) NAQS_DEEP(6) NAQS_DEEP(7) NAQS_DEEP(8)
-#undef NAQS_DEEP
-            default: return NAQS_ERR_UNSUPPORTED;
-        }
-        HIP_TRY(hipGetLastError());
-        std::snprintf(net->last_deep, sizeof(net->last_deep), "backward: amp_deep_backward_kernel<%d, L=%d> + amp_deep_backward_raw_kernel<%d, L=%d>",
-                      net->dims.Ha >> 4, net->amp_depth, d.Ha >> 4, net->amp_depth);
+        const naqs::DeepAmp da = naqs::deep_blocks(set);
+        st = naqs::dispatch_width(d.Ha >> 4, [&](auto c) -> int {
+            constexpr int C = decltype(c)::value;
+            if (set.raw) {                                  // deep phase blocks
+                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&amp_deep_backward_raw_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
+                NAQS_KLAUNCH(amp_deep_backward_raw_kernel<C>, dim3((unsigned)n_wg, (unsigned)d.P), dim3(naqs::DBW * WAVE), lds_d, s, d, set.w, da, M,
+                             keys_dev, g_dev, 1, gpart, stride);
+            } else {                                        // deep amplitude blocks
+                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&amp_deep_backward_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
+                NAQS_KLAUNCH(amp_deep_backward_kernel<C>, dim3((unsigned)n_wg, (unsigned)d.P), dim3(naqs::DBW * WAVE), lds_d, s, d, set.w, da, M,
+                             keys_dev, g_dev, gpart, stride);
+            }
+            HIP_TRY(hipGetLastError());
+            return NAQS_OK;
+        });
+        if (st != NAQS_OK) return st;
+        if (set.raw)
+            std::snprintf(net->last_deep, sizeof(net->last_deep), "backward: amp_deep_backward_kernel<%d, L=%d> + amp_deep_backward_raw_kernel<%d, L=%d>",
+                          net->amp.d.Ha >> 4, net->amp.depth, d.Ha >> 4, set.depth);
+        else
+            std::snprintf(net->last_deep, sizeof(net->last_deep), "backward: amp_deep_backward_kernel<%d, L=%d>", d.Ha >> 4, set.depth);
     } else {
         const int NW = d.Ha >> 4;
         const size_t lds = naqs::ampbw::smem_floats(d) * sizeof(float);
@@ -378,37 +375,33 @@ int naqs::net_blocks_backward(naqs_net *net, const NetDims &d, const float *w, c
             HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&amp_backward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
             net->grad_attr_set = true;
         }
-        AmpSrc src;
-        for (int n = 0; n < MAXP; ++n) src.off[n] = src_off[n] - src_off[0];         // relative to this set's first parameter
-        NAQS_KLAUNCH(amp_backward_kernel, dim3((unsigned)n_wg, (unsigned)d.P), dim3((unsigned)(NW * WAVE)), lds, s, d, w, M, keys_dev,
-                           g_dev, gpart, stride, src, raw);
+        NAQS_KLAUNCH(amp_backward_kernel, dim3((unsigned)n_wg, (unsigned)d.P), dim3((unsigned)(NW * WAVE)), lds, s, d, set.w, M, keys_dev,
+                           g_dev, gpart, stride, naqs::block_src<AmpSrc>(set, /*relative=*/true), set.raw ? 1 : 0);
         HIP_TRY(hipGetLastError());
     }
     if (defer) {
-        defer->count = n_block_params; defer->stride = stride; defer->n_partials = n_wg; defer->partial = gpart;
+        defer->count = set.n_params; defer->stride = stride; defer->n_partials = n_wg; defer->partial = gpart;
         return NAQS_OK;
     }
-    NAQS_KLAUNCH(amp_reduce_kernel, dim3((unsigned)((n_block_params + 255) / 256)), dim3(256), 0, s, n_block_params, n_wg,
+    NAQS_KLAUNCH(amp_reduce_kernel, dim3((unsigned)((set.n_params + 255) / 256)), dim3(256), 0, s, set.n_params, n_wg,
                        stride, gpart, grad_dev);
     HIP_TRY(hipGetLastError());
     return NAQS_OK;
 }
 
 // what net_blocks_backward would launch, for a caller that runs the workgroups inside a launch of its own
-// (naqs_phase_grad.hip: backward_mega_kernel): the partial-sum scratch (allocated on first use), the reduction it needs
-// afterwards and the pairs' offsets
-int naqs::net_blocks_backward_plan(naqs_net *net, const NetDims &d, const int64_t *src_off, int64_t n_block_params, int64_t M, int slot,
-                                   BlockReduceJob *job, naqs::ampbw::AmpSrc *src) {
+// (naqs_phase_grad.hip: backward_mega_kernel): the partial-sum scratch, the reduction it needs afterwards and the pairs' offsets
+int naqs::net_blocks_backward_plan(naqs_net *net, const BlockSet &set, int64_t M, int slot, BlockReduceJob *job, naqs::ampbw::AmpSrc *src) {
+    const NetDims &d = set.d;
     if (d.Ha > 128 || (d.Ha & 15) || M <= 0 || !job || !src) return NAQS_ERR_INVALID;
-    if (net->amp_depth > 1 && &d == &net->dims) return NAQS_ERR_UNSUPPORTED;       // (deep blocks: net_blocks_backward's own launch)
-    const int n_wg = (int)std::min<int64_t>(MAX_TILE_WGS, (M + GT - 1) / GT);
-    const int64_t stride = (std::max(net->amp_params, net->ph_params) + 3) & ~3ll;
-    if (!net->d_gpart) {
-        HIP_TRY(hipMalloc((void **)&net->d_gpart, 2 * (size_t)MAX_TILE_WGS * stride * sizeof(float)));
-    }
-    job->count = n_block_params; job->stride = stride; job->n_partials = n_wg;
-    job->partial = net->d_gpart + (slot ? (size_t)MAX_TILE_WGS * stride : 0);
-    for (int n = 0; n < MAXP; ++n) src->off[n] = src_off[n] - src_off[0];
+    if (set.deep()) return NAQS_ERR_UNSUPPORTED;           // (deep blocks: net_blocks_backward's own launch)
+    int64_t stride;
+    float *gpart;
+    const int st = blocks_partials(net, slot, &stride, &gpart);
+    if (st != NAQS_OK) return st;
+    job->count = set.n_params; job->stride = stride; job->n_partials = (int)std::min<int64_t>(MAX_TILE_WGS, (M + GT - 1) / GT);
+    job->partial = gpart;
+    *src = naqs::block_src<AmpSrc>(set, /*relative=*/true);
     return NAQS_OK;
 }
 
@@ -416,40 +409,39 @@ int naqs::net_blocks_backward_plan(naqs_net *net, const NetDims &d, const int64_
 // to the caller like net_blocks_backward's with `defer`
 int naqs::net_blocks_backward2(naqs_net *net, int64_t M, const uint64_t *keys_dev, const float *g_amp, const float *g_ph, int g_stride,
                                BlockReduceJob jobs[2], hipStream_t s) {
-    const NetDims &d0 = net->dims, &d1 = net->dph;
+    const NetDims &d0 = net->amp.d, &d1 = net->ph.d;
     if (d0.Ha != d1.Ha || d0.P != d1.P || M <= 0) return NAQS_ERR_INVALID;
-    if (net->amp_depth > 1) {                     // deep blocks (naqs_net_create_agg_layers): agg_deep_backward_kernel, same partials
-        if (d0.Ha > 128 || (d0.Ha & 15) || !net->aggregate) return NAQS_ERR_UNSUPPORTED;
+    if (net->amp.deep()) {                        // deep blocks (naqs_net_create_agg_layers): agg_deep_backward_kernel, same partials
+        if (d0.Ha > 128 || (d0.Ha & 15) || net->family != naqs::Family::AGGREGATE) return NAQS_ERR_UNSUPPORTED;
         const int n_wg = (int)std::min<int64_t>(MAX_TILE_WGS, (M + GT - 1) / GT);
-        const int64_t stride = (std::max(net->amp_params, net->ph_params) + 3) & ~3ll;
-        if (!net->d_gpart) HIP_TRY(hipMalloc((void **)&net->d_gpart, 2 * (size_t)MAX_TILE_WGS * stride * sizeof(float)));
-        const size_t lds_d = naqs::deep_bw_smem_floats(d0.Ha, net->amp_depth) * sizeof(float);
-        if (lds_d > 156 * 1024) return NAQS_ERR_UNSUPPORTED;
-        jobs[0].count = net->amp_params; jobs[1].count = net->ph_params;
+        const size_t lds_d = naqs::deep_bw_smem_floats(d0.Ha, net->amp.depth) * sizeof(float);
+        jobs[0].count = net->amp.n_params; jobs[1].count = net->ph.n_params;
         for (int k = 0; k < 2; ++k) {
-            jobs[k].stride = stride; jobs[k].n_partials = n_wg;
-            jobs[k].partial = net->d_gpart + (k ? (size_t)MAX_TILE_WGS * stride : 0);
+            float *gpart;
+            const int stp = blocks_partials(net, k, &jobs[k].stride, &gpart);
+            if (stp != NAQS_OK) return stp;
+            jobs[k].n_partials = n_wg; jobs[k].partial = gpart;
         }
-        const naqs::DeepAmp da0 = naqs::deep_amp(net), da1 = naqs::deep_phase(net);
-        switch (d0.Ha >> 4) {
-#define NAQS_DEEP(C) case C:                                                                                                              \
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&agg_deep_backward_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024)); \
-            NAQS_KLAUNCH(agg_deep_backward_kernel<C>, dim3((unsigned)n_wg, (unsigned)d0.P, 2), dim3(naqs::DBW * WAVE), lds_d, s, d0, net->d_wdeep, da0, \
-                         const_cast<float *>(jobs[0].partial), d1, net->d_wph, da1, const_cast<float *>(jobs[1].partial), M, keys_dev, g_amp, g_ph, \
-                         g_stride, stride);                                                                                                \
-            break;
-            NAQS_DEEP(1) NAQS_DEEP(2) NAQS_DEEP(3) NAQS_DEEP(4) NAQS_DEEP(5) NAQS_DEEP(6) NAQS_DEEP(7) NAQS_DEEP(8)
-#undef NAQS_DEEP
-            default: return NAQS_ERR_UNSUPPORTED;
-        }
-        HIP_TRY(hipGetLastError());
-        std::snprintf(net->last_deep, sizeof(net->last_deep), "backward: agg_deep_backward_kernel<%d, L=%d>", d0.Ha >> 4, net->amp_depth);
+        if (lds_d > 156 * 1024) return NAQS_ERR_UNSUPPORTED;
+        const int64_t stride = jobs[0].stride;
+        const naqs::DeepAmp da0 = naqs::deep_blocks(net->amp), da1 = naqs::deep_blocks(net->ph);
+        const int st = naqs::dispatch_width(d0.Ha >> 4, [&](auto c) -> int {
+            constexpr int C = decltype(c)::value;
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&agg_deep_backward_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
+            NAQS_KLAUNCH(agg_deep_backward_kernel<C>, dim3((unsigned)n_wg, (unsigned)d0.P, 2), dim3(naqs::DBW * WAVE), lds_d, s, d0, net->amp.w, da0,
+                         const_cast<float *>(jobs[0].partial), d1, net->ph.w, da1, const_cast<float *>(jobs[1].partial), M, keys_dev, g_amp, g_ph,
+                         g_stride, stride);
+            HIP_TRY(hipGetLastError());
+            return NAQS_OK;
+        });
+        if (st != NAQS_OK) return st;
+        std::snprintf(net->last_deep, sizeof(net->last_deep), "backward: agg_deep_backward_kernel<%d, L=%d>", d0.Ha >> 4, net->amp.depth);
         return NAQS_OK;
     }
     AmpSrc src0, src1;
-    int st = net_blocks_backward_plan(net, d0, net->amp_src_off, net->amp_params, M, 0, &jobs[0], &src0);
+    int st = net_blocks_backward_plan(net, net->amp, M, 0, &jobs[0], &src0);
     if (st != NAQS_OK) return st;
-    st = net_blocks_backward_plan(net, d1, net->ph_src_off, net->ph_params, M, 1, &jobs[1], &src1);
+    st = net_blocks_backward_plan(net, net->ph, M, 1, &jobs[1], &src1);
     if (st != NAQS_OK) return st;
     const size_t lds = std::max(naqs::ampbw::smem_floats(d0), naqs::ampbw::smem_floats(d1)) * sizeof(float);
     if (lds > 156 * 1024) return NAQS_ERR_UNSUPPORTED;
@@ -458,7 +450,7 @@ int naqs::net_blocks_backward2(naqs_net *net, int64_t M, const uint64_t *keys_de
         net->grad2_attr_set = true;
     }
     NAQS_KLAUNCH(amp_backward2_kernel, dim3((unsigned)jobs[0].n_partials, (unsigned)d0.P, 2), dim3((unsigned)((d0.Ha >> 4) * WAVE)), lds, s,
-                       d0, net->d_w, const_cast<float *>(jobs[0].partial), src0, d1, net->d_wph, const_cast<float *>(jobs[1].partial), src1, M,
+                       d0, net->amp.w, const_cast<float *>(jobs[0].partial), src0, d1, net->ph.w, const_cast<float *>(jobs[1].partial), src1, M,
                        keys_dev, g_amp, g_ph, jobs[0].stride, g_stride);
     HIP_TRY(hipGetLastError());
     return NAQS_OK;
@@ -466,8 +458,8 @@ int naqs::net_blocks_backward2(naqs_net *net, int64_t M, const uint64_t *keys_de
 
 int naqs::net_comb_backward(naqs_net *net, int64_t M, const uint64_t *keys_dev, const float *g_dev, int g_stride, bool with_head,
                              float *grad_dev, const naqs::AdamArgs *adam, hipStream_t s) {
-    const NetDims &d0 = net->dims, &d1 = net->dph;
-    if (!net->comb || d0.Ha > 128 || (d0.Ha & 15) || d1.Ha != d0.Ha || d1.P != d0.P) return NAQS_ERR_UNSUPPORTED;
+    const NetDims &d0 = net->amp.d, &d1 = net->ph.d;
+    if (net->family != naqs::Family::COMBINED || d0.Ha > 128 || (d0.Ha & 15) || d1.Ha != d0.Ha || d1.P != d0.P) return NAQS_ERR_UNSUPPORTED;
     if (M <= 0) {
         if (adam) return NAQS_ERR_INVALID;
         HIP_TRY(hipMemsetAsync(grad_dev, 0, (size_t)net->n_params * sizeof(float), s));
@@ -482,10 +474,9 @@ int naqs::net_comb_backward(naqs_net *net, int64_t M, const uint64_t *keys_dev, 
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&comb_backward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
         net->comb_attr_set = true;
     }
-    AmpSrc src;
-    for (int n = 0; n < MAXP; ++n) src.off[n] = net->amp_src_off[n] - net->amp_src_off[0];
+    const AmpSrc src = naqs::block_src<AmpSrc>(net->amp, /*relative=*/true);
     NAQS_KLAUNCH(comb_backward_kernel, dim3((unsigned)n_wg, (unsigned)(d0.P + (with_head ? 1 : 0))), dim3((unsigned)((d0.Ha >> 4) * WAVE)), lds, s,
-                       d0, net->d_w, src, d1, net->d_wph, net->comb_amp, M, keys_dev, g_dev, g_stride, net->d_cpart, stride);
+                       d0, net->amp.w, src, d1, net->ph.w, net->comb_amp, M, keys_dev, g_dev, g_stride, net->d_cpart, stride);
     HIP_TRY(hipGetLastError());
     const naqs::CombLayout c = naqs::comb_layout(net);
     NAQS_KLAUNCH(comb_grad_finish_kernel, dim3((unsigned)((c.total + 255) / 256)), dim3(256), 0, s, c, n_wg, stride, net->d_cpart,
@@ -504,7 +495,7 @@ NAQS_API int naqs_net_amp_backward(naqs_net_t *net, int64_t M, const uint64_t *k
     st = naqs::net_flush_amp_pack(net, reinterpret_cast<hipStream_t>(stream));
     if (st != NAQS_OK) return st;
     // combined blocks: log|psi| only — the phase rows get zero gradient, the flat layout is the whole parameter vector's
-    if (net->comb) return naqs::net_comb_backward(net, M, keys_dev, g_dev, 1, false, grad_dev, nullptr, reinterpret_cast<hipStream_t>(stream));
-    return naqs::net_blocks_backward(net, net->dims, net->d_w, net->amp_src_off, net->amp_params, M, keys_dev, g_dev, grad_dev, 0,
-                                     reinterpret_cast<hipStream_t>(stream));
+    if (net->family == naqs::Family::COMBINED)
+        return naqs::net_comb_backward(net, M, keys_dev, g_dev, 1, false, grad_dev, nullptr, reinterpret_cast<hipStream_t>(stream));
+    return naqs::net_blocks_backward(net, net->amp, M, keys_dev, g_dev, grad_dev, reinterpret_cast<hipStream_t>(stream));
 }

@@ -75,7 +75,7 @@ __device__ __forceinline__ void amp_body(const NetDims &d, const float *__restri
     const int tile = wave / AMP_SPLIT, q = wave % AMP_SPLIT;
     const int n = blockIdx.y;            // workgroup-uniform
     const int nin = n == 0 ? 1 : 2 * n;
-    const int S = (nin + 1 + 5 + 3) & ~3;
+    const int S = naqs::amp_row_stride(nin);
     {
         const int total = d.Ha * S + 8;
         const f32x4 *src = reinterpret_cast<const f32x4 *>(w + d.amp_off[n]);      // offsets are multiples of 4 floats
@@ -173,7 +173,7 @@ __global__ __launch_bounds__(256) void agg_finish_kernel(const int P, const int6
 }
 
 // combined amplitude-phase blocks (naqs_net_create_combined): the phase head — the last block's hidden layer and phase rows, a raw
-// block of pair P - 1 (d = net->dph) — through amp_body, which writes row P - 1 of `scratch`.  The launch has amp_kernel's shape;
+// block of pair P - 1 (d = net->ph.d) — through amp_body, which writes row P - 1 of `scratch`.  The launch has amp_kernel's shape;
 // the workgroups of the other pairs leave at once.
 __global__ __launch_bounds__(AMP_TILES * AMP_SPLIT * WAVE) void comb_head_kernel(const NetDims d, const float *__restrict__ w,
                                                                                  int64_t M, const uint64_t *__restrict__ keys,
@@ -1005,7 +1005,7 @@ __global__ __launch_bounds__(DEEPK_WAVES * 64) void amp_deep_kernel(const NetDim
 }
 
 // Aggregate phase with deep blocks (naqs_net_create_agg_layers): one (tile, pair) item of either set, amp_deep_kernel's arithmetic.
-// RAW (d = net->dph, the per-pair phase blocks): the realised outcome's output is the pair's phase, as amp_body's raw mode has it —
+// RAW (d = net->ph.d, the per-pair phase blocks): the realised outcome's output is the pair's phase, as amp_body's raw mode has it —
 // row phase_out_row(occ), and the last block's phase carries phase_sym_shift (nade.py:597-610, :758-759).
 template <int CT, bool RAW>
 __device__ __forceinline__ void amp_deep_body(const NetDims &d, const float *__restrict__ wdeep, const naqs::DeepAmp &da, const int64_t M,
@@ -1832,18 +1832,23 @@ __global__ __launch_bounds__(256) void pack_net_kernel(const float *__restrict__
 
 }  // namespace
 
-NAQS_API int naqs_net_create(const naqs_net_config_t *cfg, int device, naqs_net_t **out) {
-    if (!cfg || !out) return NAQS_ERR_INVALID;
-    *out = nullptr;
+// ---- creating a handle: validate, lay the whole handle out on the host, allocate what the family's kernels read ----
+
+static naqs::Family family_of(const naqs_net_config_t *cfg) { return cfg->aggregate_phase != 0 ? naqs::Family::AGGREGATE : naqs::Family::SINGLE_PHASE; }
+// deep blocks run on 16-unit hidden tiles, at most 8 of them
+static bool deep_width_ok(const int H) { return H > 0 && !(H & 15) && H <= 128; }
+
+// the checks of the config every entry point shares, in their order of precedence; the device's existence comes last
+static int net_validate(const naqs_net_config_t *cfg, const naqs::Family family, const int depth, const int device) {
     const int N = cfg->n_qubits;
     if (N <= 0 || (N & 1)) return NAQS_ERR_INVALID;
     const int P = N / 2;
     if (P > MAXP) return NAQS_ERR_UNSUPPORTED;
     if (P < 2) return NAQS_ERR_UNSUPPORTED;
-    if (cfg->amp_hidden <= 0 || cfg->n_phase_hidden < 1 || cfg->n_phase_hidden > NAQS_NET_MAX_PHASE_LAYERS)
-        return NAQS_ERR_INVALID;
-    const bool aggregate = cfg->aggregate_phase != 0;
-    if (aggregate && (cfg->n_phase_hidden != 1 || cfg->phase_hidden[0] <= 0)) return NAQS_ERR_UNSUPPORTED;
+    if (cfg->amp_hidden <= 0) return NAQS_ERR_INVALID;
+    // (COMBINED has no phase layers of its own: it does not read their count or widths)
+    if (family != naqs::Family::COMBINED && (cfg->n_phase_hidden < 1 || cfg->n_phase_hidden > NAQS_NET_MAX_PHASE_LAYERS)) return NAQS_ERR_INVALID;
+    if (family == naqs::Family::AGGREGATE && (cfg->n_phase_hidden != depth || cfg->phase_hidden[0] <= 0)) return NAQS_ERR_UNSUPPORTED;
     if (cfg->masking < 0 || cfg->masking > 2) return NAQS_ERR_INVALID;
     if ((cfg->n_alpha < 0) != (cfg->n_beta < 0)) return NAQS_ERR_INVALID;
     std::vector<bool> seen((size_t)N, false);
@@ -1855,85 +1860,44 @@ NAQS_API int naqs_net_create(const naqs_net_config_t *cfg, int device, naqs_net_
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return NAQS_ERR_NO_DEVICE;
     if (device < 0 || device >= ndev) return NAQS_ERR_INVALID;
+    return NAQS_OK;
+}
 
-    naqs_net *net = new (std::nothrow) naqs_net();
-    if (!net) return NAQS_ERR_NOMEM;
-    net->device = device;
-    (void)naqs::poll_handle_create(device, &net->poll);
-    net->ctl = net->poll.dev;
-    net->shared_gpu = naqs::env_int("NAQS_SHARED_GPU", 0) == 1;    // (naqs_net_share_device: the same switch per handle)
-    net->cfg = *cfg;
-    NetDims &d = net->dims;
-    d.P = P;
-    d.n_alpha = cfg->n_alpha; d.n_beta = cfg->n_beta;
-    d.n_alpha_down = (N + 1) / 2 - cfg->n_alpha; d.n_beta_down = N / 2 - cfg->n_beta;
-    d.min_n_set = cfg->n_alpha < 0 ? 0 : std::min(std::min(d.n_alpha, d.n_beta), std::min(d.n_alpha_down, d.n_beta_down));
-    d.masking = cfg->masking;
-    d.sym = cfg->use_amp_spin_sym ? 1 : 0;
-    d.phase_sym = cfg->use_phase_spin_sym ? 1 : 0;
-    const int n_out_phase = d.phase_sym ? 3 : 4;               // nade.py:281
-    d.Ha = cfg->amp_hidden;
-    d.n_out_amp = d.sym ? 5 : 4;
-    for (int n = 0; n < P; ++n) { d.qa[n] = (uint8_t)cfg->qubit2model[2 * n]; d.qb[n] = (uint8_t)cfg->qubit2model[2 * n + 1]; }
-    int64_t off = 0, poff = 0;
-    for (int n = 0; n < P; ++n) {
-        net->amp_src_off[n] = off;
+// the depth-1 row layout of a set (NetDims::amp_off: part of every kernel's NetDims whatever the depth) and its size
+static void layout_rows(NetDims &d) {
+    int64_t poff = 0;
+    for (int n = 0; n < d.P; ++n) {
         d.amp_off[n] = (int32_t)poff;
-        const int nin = n == 0 ? 1 : 2 * n;
-        off += (int64_t)d.Ha * nin + d.Ha + (int64_t)d.n_out_amp * d.Ha + d.n_out_amp;
-        poff += (int64_t)d.Ha * ((nin + 1 + 5 + 3) & ~3) + 8;
+        poff += naqs::amp_block_floats(d.Ha, n == 0 ? 1 : 2 * n);
     }
-    net->amp_params = off;
-    net->aggregate = aggregate;
-    if (aggregate) {
-        // phase blocks as a second amplitude-shaped network: same inputs, Hp hidden units, 4 raw outputs, no symmetry
-        NetDims &q = net->dph;
-        q = d;
-        q.Ha = cfg->phase_hidden[0];
-        q.sym = 0;
-        q.n_out_amp = n_out_phase;             // (-phase_sym: 3 raw outputs, the middle one for |01> and |10>; q.phase_sym orders the inputs)
-        int64_t poff2 = 0;
-        for (int n = 0; n < P; ++n) {
-            net->ph_src_off[n] = off;
-            q.amp_off[n] = (int32_t)poff2;
-            const int nin = n == 0 ? 1 : 2 * n;
-            off += (int64_t)q.Ha * nin + q.Ha + (int64_t)n_out_phase * q.Ha + n_out_phase;
-            poff2 += (int64_t)q.Ha * ((nin + 1 + 5 + 3) & ~3) + 8;
-        }
-        net->ph_params = off - net->amp_params;
-        net->n_params = off;
-        net->w_floats = poff;
-        d.n_lin = 0;
-        d.ld = d.ldh = 0;
-        DeviceGuard guard0;
-        int st0 = guard0.init(device);
-        if (st0 == NAQS_OK) {
-            hipDeviceProp_t prop;
-            if (hipGetDeviceProperties(&prop, device) == hipSuccess) net->cu_count = prop.multiProcessorCount;
-            if (hipMalloc((void **)&net->d_w, (size_t)poff * sizeof(float)) != hipSuccess) st0 = NAQS_ERR_NOMEM;
-            if (st0 == NAQS_OK && hipMalloc((void **)&net->d_wph, (size_t)poff2 * sizeof(float)) != hipSuccess) st0 = NAQS_ERR_NOMEM;
-            // the amplitude blocks as matrix-core fragments too: the sampler's block MLP (the forward pass of this family keeps
-            // the one merged VALU launch for both sets of blocks)
-            if (st0 == NAQS_OK && (d.Ha == 32 || d.Ha == 64 || d.Ha == 128) && 2 * (P - 1) <= 30) {
-                const size_t elems = (size_t)P * amp_mfma_pair_elems(d.Ha);
-                if (hipMalloc((void **)&net->d_wamp, elems * sizeof(unsigned short)) != hipSuccess) st0 = NAQS_ERR_NOMEM;
-            }
-        }
-        if (st0 != NAQS_OK) { naqs_net_destroy(net); return st0; }
-        *out = net;
-        return NAQS_OK;
+}
+static int64_t rows_floats(const NetDims &d) { return (int64_t)d.amp_off[d.P - 1] + naqs::amp_block_floats(d.Ha, 2 * (d.P - 1)); }
+// a set's blocks in the flat source from `src` on (state_dict order, block by block) and, deep, in the 16-byte aligned copy
+static void layout_source(naqs::BlockSet &b, const int depth, int64_t &src) {
+    const int64_t src0 = src;
+    b.depth = depth;
+    for (int n = 0; n < b.d.P; ++n) {
+        const int64_t f = naqs::deep_pair_floats(b.d.Ha, b.d.n_out_amp, depth, n);
+        b.src_off[n] = src;
+        src += f;
+        if (depth > 1) { b.deep_off[n] = b.deep_floats; b.deep_floats += (f + 3) & ~3ll; }
     }
-    // phase block: 2(P-1) -> hidden... -> 4
+    b.n_params = src - src0;
+}
+// the phase MLP 2(P-1) -> hidden... -> n_out_phase: its parameters from `src` on in the flat source, its tiles from `dst` on in d_w
+static int layout_phase_mlp(naqs_net *net, const int n_out_phase, int64_t src, int64_t dst) {
+    const naqs_net_config_t *cfg = &net->cfg;
+    NetDims &d = net->amp.d;
+    const int P = d.P;
     int K = std::max(1, 2 * (P - 1));
     d.n_lin = cfg->n_phase_hidden + 1;
-    int64_t src = off, dst = poff;
     int max_k = 0;
     for (int l = 0; l < d.n_lin; ++l) {
         const int Nout = l < cfg->n_phase_hidden ? cfg->phase_hidden[l] : n_out_phase;
-        if (Nout <= 0) { delete net; return NAQS_ERR_INVALID; }
+        if (Nout <= 0) return NAQS_ERR_INVALID;
         d.K_pad[l] = (K + 15) & ~15;
         d.N_pad[l] = (Nout + 15) & ~15;
-        if (d.N_pad[l] > PH_WAVES * CBT * 16) { delete net; return NAQS_ERR_UNSUPPORTED; }   // <= 512 outputs per layer
+        if (d.N_pad[l] > PH_WAVES * CBT * 16) return NAQS_ERR_UNSUPPORTED;   // <= 512 outputs per layer
         dst = (dst + 3) & ~3ll;                                   // 16-byte aligned rows for the float4 weight loads
         d.w_off[l] = (int32_t)dst; dst += (int64_t)d.N_pad[l] * d.K_pad[l];
         d.b_off[l] = (int32_t)dst; dst += d.N_pad[l];
@@ -1960,88 +1924,152 @@ NAQS_API int naqs_net_create(const naqs_net_config_t *cfg, int device, naqs_net_
     }
     net->n_params = src;
     net->w_floats = dst;
+    // the activation tile of 48/64 rows x 516 floats exceeds the 64 KiB default of dynamic LDS; 160 KiB is all there is
+    if (4 * 16 * d.ld * (int)sizeof(float) > 160 * 1024) return NAQS_ERR_UNSUPPORTED;
+    return NAQS_OK;
+}
 
-    DeviceGuard guard;
-    int st = guard.init(device);
-    if (st == NAQS_OK) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) == hipSuccess) net->cu_count = prop.multiProcessorCount;
-        if (hipMalloc((void **)&net->d_w, (size_t)net->w_floats * sizeof(float)) != hipSuccess) st = NAQS_ERR_NOMEM;
-        if (st == NAQS_OK && hipMalloc((void **)&net->d_wh, (size_t)net->wh_elems * sizeof(unsigned short)) != hipSuccess) st = NAQS_ERR_NOMEM;
-        if (st == NAQS_OK && (d.Ha == 32 || d.Ha == 64 || d.Ha == 128)) {   // amplitude blocks as MFMA fragments (phase kernel prologue);
-            const size_t elems = (size_t)P * amp_mfma_pair_elems(d.Ha);   // input slot 31 must be free for the bias: 2 (P - 1) <= 30
-            if (hipMalloc((void **)&net->d_wamp, elems * sizeof(unsigned short)) != hipSuccess) st = NAQS_ERR_NOMEM;
+// Everything a handle of net->family with blocks of `depth` hidden layers is, from net->cfg: both NetDims, both block sets' offsets,
+// the phase MLP's tables or the combined layout, n_params.  Host arithmetic only.
+static int net_layout(naqs_net *net, const int depth) {
+    const naqs_net_config_t *cfg = &net->cfg;
+    const int N = cfg->n_qubits, P = N / 2;
+    NetDims &d = net->amp.d;
+    d.P = P;
+    d.n_alpha = cfg->n_alpha; d.n_beta = cfg->n_beta;
+    d.n_alpha_down = (N + 1) / 2 - cfg->n_alpha; d.n_beta_down = N / 2 - cfg->n_beta;
+    d.min_n_set = cfg->n_alpha < 0 ? 0 : std::min(std::min(d.n_alpha, d.n_beta), std::min(d.n_alpha_down, d.n_beta_down));
+    d.masking = cfg->masking;
+    d.sym = cfg->use_amp_spin_sym ? 1 : 0;
+    d.phase_sym = cfg->use_phase_spin_sym ? 1 : 0;
+    const int n_out_phase = d.phase_sym ? 3 : 4;               // nade.py:281
+    d.Ha = cfg->amp_hidden;
+    d.n_out_amp = d.sym ? 5 : 4;
+    for (int n = 0; n < P; ++n) { d.qa[n] = (uint8_t)cfg->qubit2model[2 * n]; d.qb[n] = (uint8_t)cfg->qubit2model[2 * n + 1]; }
+    layout_rows(d);
+    int64_t src = 0;
+    layout_source(net->amp, depth, src);
+    net->w_floats = rows_floats(d);
+    if (naqs::has_phase_mlp(net)) return layout_phase_mlp(net, n_out_phase, src, net->w_floats);
+    // the second set as an amplitude-shaped network on the same inputs: raw outputs, no amplitude symmetry (-phase_sym: 3 raw
+    // outputs, the middle one for |01> and |10>; its phase_sym orders the inputs)
+    naqs::BlockSet &h = net->ph;
+    h.raw = true;
+    h.d = d;
+    h.d.sym = 0;
+    h.d.n_out_amp = n_out_phase;
+    switch (net->family) {
+        case naqs::Family::SINGLE_PHASE: break;
+        case naqs::Family::AGGREGATE:                          // per-pair phase blocks of their own width behind the amplitude blocks
+            h.d.Ha = cfg->phase_hidden[0];
+            layout_rows(h.d);
+            layout_source(h, depth, src);
+            net->n_params = src;
+            break;
+        case naqs::Family::COMBINED: {                         // the head: the amplitude width, no parameters of its own in the source
+            layout_rows(h.d);
+            const int64_t nin = 2 * (P - 1), nph = n_out_phase;
+            net->comb_amp = net->amp.n_params;
+            net->comb_head = d.Ha * nin + d.Ha + nph * d.Ha + nph;
+            net->n_params = net->comb_amp + nph * d.Ha + nph;
+            net->amp.n_params = net->n_params;                 // (no phase layers: every parameter belongs to the blocks)
+            break;
         }
-        // the activation tile of 48/64 rows x 516 floats exceeds the 64 KiB default of dynamic LDS
-        const int lds_max = 4 * 16 * d.ld * (int)sizeof(float);
-        if (lds_max > 160 * 1024) st = NAQS_ERR_UNSUPPORTED;
-        if (st == NAQS_OK) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&phase_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max / 4);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&phase_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max / 2);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&phase_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max / 4 * 3);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&phase_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-            // (the amplitude prologue's scratch can exceed one 16-row slab: allow the maximum for every variant)
-            const int lds_all = 160 * 1024 - 5 * 1024;         // the static part (s_ab, s_lan) is < 5 KiB for every RB
+    }
+    return NAQS_OK;
+}
+
+template <typename T>
+static int dev_alloc(T **p, const int64_t n) { return hipMalloc((void **)p, (size_t)n * sizeof(T)) == hipSuccess ? NAQS_OK : NAQS_ERR_NOMEM; }
+
+// The device buffers of a laid-out handle — what its family's kernels read, nothing else:
+//   d_w      rows + phase MLP tiles: every handle but a deep AGGREGATE one (both sets deep, no MLP)
+//   amp.w    depth 1: d_w itself; deep: a buffer of its own
+//   ph.w     AGGREGATE / COMBINED: rows, or the deep layout
+//   d_wamp   depth-1 blocks of 32 / 64 / 128 units (per-pair families: and input slot 31 free for the bias, 2 (P - 1) <= 30)
+//   d_cflat  COMBINED;  d_wh, d_raw, d_scales, d_sum_words: the phase MLP's
+static int net_alloc(naqs_net *net) {
+    const NetDims &d = net->amp.d;
+    const bool deep = net->amp.deep(), mlp = naqs::has_phase_mlp(net);
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, net->device) == hipSuccess) net->cu_count = prop.multiProcessorCount;
+    int st = NAQS_OK;
+    if (mlp || !deep) st = dev_alloc(&net->d_w, net->w_floats);
+    if (st == NAQS_OK && deep) st = dev_alloc(&net->amp.w, net->amp.deep_floats);
+    if (!deep) net->amp.w = net->d_w;
+    if (st == NAQS_OK && naqs::has_second_set(net)) st = dev_alloc(&net->ph.w, net->ph.deep() ? net->ph.deep_floats : rows_floats(net->ph.d));
+    if (st == NAQS_OK && !deep && (d.Ha == 32 || d.Ha == 64 || d.Ha == 128) && (mlp || 2 * (d.P - 1) <= 30))
+        st = dev_alloc(&net->d_wamp, (int64_t)d.P * (int64_t)amp_mfma_pair_elems(d.Ha));
+    if (st == NAQS_OK && net->family == naqs::Family::COMBINED) st = dev_alloc(&net->d_cflat, net->comb_amp + net->comb_head);
+    if (st != NAQS_OK || !mlp) return st;
+    st = dev_alloc(&net->d_wh, net->wh_elems);
+    if (st != NAQS_OK) return st;
+    const int lds_max = 4 * 16 * d.ld * (int)sizeof(float);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&phase_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max / 4);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&phase_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max / 2);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&phase_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max / 4 * 3);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&phase_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+    // (the amplitude prologue's scratch can exceed one 16-row slab: allow the maximum for every variant)
+    const int lds_all = 160 * 1024 - 5 * 1024;         // the static part (s_ab, s_lan) is < 5 KiB for every RB
 #define NAQS_PH_ATTR(RB, FMT)                                                                                                            \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&phase_kernel_h<RB, false, FMT>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_all); \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&phase_kernel_h<RB, true, FMT>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_all);
-            NAQS_PH_ATTR(1, 1) NAQS_PH_ATTR(2, 1) NAQS_PH_ATTR(3, 1)
-            NAQS_PH_ATTR(1, 2) NAQS_PH_ATTR(2, 2) NAQS_PH_ATTR(3, 2) NAQS_PH_ATTR(4, 2)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&phase_kernel_h<RB, false, FMT>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_all); \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&phase_kernel_h<RB, true, FMT>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_all);
+    NAQS_PH_ATTR(1, 1) NAQS_PH_ATTR(2, 1) NAQS_PH_ATTR(3, 1)
+    NAQS_PH_ATTR(1, 2) NAQS_PH_ATTR(2, 2) NAQS_PH_ATTR(3, 2) NAQS_PH_ATTR(4, 2)
 #undef NAQS_PH_ATTR
 #define NAQS_WS_ATTR(RB)                                                                                                                 \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&phase_kernel_ws<RB, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_all); \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&phase_kernel_ws<RB, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_all); \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&phase_kernel_ws<RB, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_all); \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&phase_kernel_ws<RB, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_all);
-            NAQS_WS_ATTR(1) NAQS_WS_ATTR(2) NAQS_WS_ATTR(3)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&phase_kernel_ws<RB, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_all); \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&phase_kernel_ws<RB, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_all); \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&phase_kernel_ws<RB, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_all); \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&phase_kernel_ws<RB, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_all);
+    NAQS_WS_ATTR(1) NAQS_WS_ATTR(2) NAQS_WS_ATTR(3)
 #undef NAQS_WS_ATTR
-            (void)hipGetLastError();            // a refused attribute must not stay behind as the runtime's "last error"
-        }
-        if (st == NAQS_OK && hipMalloc((void **)&net->d_raw, sizeof(naqs::PhaseRaw)) != hipSuccess) st = NAQS_ERR_NOMEM;
-        if (st == NAQS_OK && hipMalloc((void **)&net->d_scales, sizeof(naqs::PhaseScales)) != hipSuccess) st = NAQS_ERR_NOMEM;
-        if (st == NAQS_OK && hipMemset(net->d_raw, 0, sizeof(naqs::PhaseRaw)) != hipSuccess) st = NAQS_ERR_HIP;
-        if (st == NAQS_OK && hipMalloc((void **)&net->d_sum_words, 8 * sizeof(unsigned long long)) != hipSuccess) st = NAQS_ERR_NOMEM;
-        if (st == NAQS_OK && hipMemset(net->d_sum_words, 0, 8 * sizeof(unsigned long long)) != hipSuccess) st = NAQS_ERR_HIP;
-        if (st == NAQS_OK && hipDeviceSynchronize() != hipSuccess) st = NAQS_ERR_HIP;     // null-stream fill: done before any non-blocking stream writes there
-    }
+    (void)hipGetLastError();            // a refused attribute must not stay behind as the runtime's "last error"
+    st = dev_alloc(&net->d_raw, 1);
+    if (st == NAQS_OK) st = dev_alloc(&net->d_scales, 1);
+    if (st == NAQS_OK && hipMemset(net->d_raw, 0, sizeof(naqs::PhaseRaw)) != hipSuccess) st = NAQS_ERR_HIP;
+    if (st == NAQS_OK) st = dev_alloc(&net->d_sum_words, 8);
+    if (st == NAQS_OK && hipMemset(net->d_sum_words, 0, 8 * sizeof(unsigned long long)) != hipSuccess) st = NAQS_ERR_HIP;
+    if (st == NAQS_OK && hipDeviceSynchronize() != hipSuccess) st = NAQS_ERR_HIP;     // null-stream fill: done before any non-blocking stream writes there
+    return st;
+}
+
+// the one builder behind the four create entry points (theirs: the checks of their own arguments)
+static int net_build(const naqs_net_config_t *cfg, const naqs::Family family, const int depth, const int device, naqs_net_t **out) {
+    int st = net_validate(cfg, family, depth, device);
+    if (st != NAQS_OK) return st;
+    naqs_net *net = new (std::nothrow) naqs_net();
+    if (!net) return NAQS_ERR_NOMEM;
+    net->device = device;
+    net->cfg = *cfg;
+    net->family = family;
+    st = net_layout(net, depth);
+    if (st != NAQS_OK) { delete net; return st; }
+    (void)naqs::poll_handle_create(device, &net->poll);
+    net->ctl = net->poll.dev;
+    net->shared_gpu = naqs::env_int("NAQS_SHARED_GPU", 0) == 1;    // (naqs_net_share_device: the same switch per handle)
+    DeviceGuard guard;
+    st = guard.init(device);
+    if (st == NAQS_OK) st = net_alloc(net);
     if (st != NAQS_OK) { naqs_net_destroy(net); return st; }
     *out = net;
     return NAQS_OK;
+}
+
+NAQS_API int naqs_net_create(const naqs_net_config_t *cfg, int device, naqs_net_t **out) {
+    if (!cfg || !out) return NAQS_ERR_INVALID;
+    *out = nullptr;
+    return net_build(cfg, family_of(cfg), 1, device, out);
 }
 
 NAQS_API int naqs_net_create_amp_layers(const naqs_net_config_t *cfg, int32_t n_amp_hidden, int device, naqs_net_t **out) {
     if (!cfg || !out) return NAQS_ERR_INVALID;
     *out = nullptr;
     if (n_amp_hidden < 1 || n_amp_hidden > naqs::MAX_AMP_LAYERS) return NAQS_ERR_INVALID;
-    if (n_amp_hidden == 1) return naqs_net_create(cfg, device, out);
-    if (cfg->aggregate_phase != 0) return NAQS_ERR_UNSUPPORTED;           // (deep blocks: the single-phase family only)
-    if (cfg->amp_hidden > 0 && ((cfg->amp_hidden & 15) || cfg->amp_hidden > 128)) return NAQS_ERR_UNSUPPORTED;
-    naqs_net_t *net = nullptr;
-    int st = naqs_net_create(cfg, device, &net);
-    if (st != NAQS_OK) return st;
-    const NetDims &d = net->dims;
-    const int L = n_amp_hidden;
-    int64_t off = 0, doff = 0;
-    for (int n = 0; n < d.P; ++n) {                       // state_dict order, block by block
-        const int64_t f = naqs::deep_pair_floats(d.Ha, d.n_out_amp, L, n);
-        net->amp_src_off[n] = off;
-        net->deep_off[n] = doff;
-        off += f;
-        doff += (f + 3) & ~3ll;
-    }
-    const int64_t delta = off - net->amp_params;          // the phase layers follow the deeper blocks
-    for (int64_t &o : net->phase_src_off) o += delta;
-    net->amp_params = off;
-    net->n_params += delta;
-    net->amp_depth = L;
-    net->deep_floats = doff;
-    DeviceGuard guard;
-    st = guard.init(device);
-    if (st == NAQS_OK && net->d_wamp) { (void)hipFree(net->d_wamp); net->d_wamp = nullptr; }     // (the depth-1 fragments: never read)
-    if (st == NAQS_OK && hipMalloc((void **)&net->d_wdeep, (size_t)doff * sizeof(float)) != hipSuccess) st = NAQS_ERR_NOMEM;
-    if (st != NAQS_OK) { naqs_net_destroy(net); return st; }
-    *out = net;
-    return NAQS_OK;
+    if (n_amp_hidden == 1) return net_build(cfg, family_of(cfg), 1, device, out);
+    if (cfg->aggregate_phase != 0) return NAQS_ERR_UNSUPPORTED;           // (deep blocks + a phase MLP: the single-phase family only)
+    if (cfg->amp_hidden > 0 && !deep_width_ok(cfg->amp_hidden)) return NAQS_ERR_UNSUPPORTED;
+    return net_build(cfg, naqs::Family::SINGLE_PHASE, n_amp_hidden, device, out);
 }
 
 NAQS_API int naqs_net_create_agg_layers(const naqs_net_config_t *cfg, int32_t n_hidden, int device, naqs_net_t **out) {
@@ -2049,8 +2077,7 @@ NAQS_API int naqs_net_create_agg_layers(const naqs_net_config_t *cfg, int32_t n_
     *out = nullptr;
     if (n_hidden < 1 || n_hidden > naqs::MAX_AMP_LAYERS) return NAQS_ERR_INVALID;
     if (cfg->aggregate_phase == 0) return NAQS_ERR_UNSUPPORTED;           // (the single-phase family: naqs_net_create_amp_layers)
-    if (n_hidden == 1) return naqs_net_create(cfg, device, out);
-    // every check that needs no device comes first
+    if (n_hidden == 1) return net_build(cfg, naqs::Family::AGGREGATE, 1, device, out);
     const int N = cfg->n_qubits;
     if (N <= 0 || (N & 1)) return NAQS_ERR_INVALID;
     if (N / 2 < 2 || N / 2 > MAXP) return NAQS_ERR_UNSUPPORTED;
@@ -2058,83 +2085,18 @@ NAQS_API int naqs_net_create_agg_layers(const naqs_net_config_t *cfg, int32_t n_
     const int Hp = cfg->phase_hidden[0];
     for (int l = 1; l < n_hidden; ++l)
         if (cfg->phase_hidden[l] != Hp) return NAQS_ERR_UNSUPPORTED;
-    if (Hp <= 0 || (Hp & 15) || Hp > 128) return NAQS_ERR_UNSUPPORTED;
-    if (cfg->amp_hidden > 0 && ((cfg->amp_hidden & 15) || cfg->amp_hidden > 128)) return NAQS_ERR_UNSUPPORTED;
-    // the depth-1 aggregate handle of the same widths, whose block sets are then re-described as deep ones
-    naqs_net_config_t c = *cfg;
-    c.n_phase_hidden = 1;
-    naqs_net_t *net = nullptr;
-    int st = naqs_net_create(&c, device, &net);
-    if (st != NAQS_OK) return st;
-    net->cfg = *cfg;
-    const NetDims &d = net->dims, &q = net->dph;
-    const int L = n_hidden;
-    int64_t off = 0, doff = 0;
-    for (int n = 0; n < d.P; ++n) {                       // amplitude blocks: exactly naqs_net_create_amp_layers' layout
-        const int64_t f = naqs::deep_pair_floats(d.Ha, d.n_out_amp, L, n);
-        net->amp_src_off[n] = off;
-        net->deep_off[n] = doff;
-        off += f;
-        doff += (f + 3) & ~3ll;
-    }
-    net->amp_params = off;
-    net->amp_depth = L;
-    net->deep_floats = doff;
-    int64_t poff = 0;
-    for (int n = 0; n < q.P; ++n) {                       // then the phase blocks, block by block
-        const int64_t f = naqs::deep_pair_floats(q.Ha, q.n_out_amp, L, n);
-        net->ph_src_off[n] = off;
-        net->ph_deep_off[n] = poff;
-        off += f;
-        poff += (f + 3) & ~3ll;
-    }
-    net->ph_params = off - net->amp_params;
-    net->n_params = off;
-    net->ph_deep_floats = poff;
-    DeviceGuard guard;
-    st = guard.init(device);
-    if (st == NAQS_OK && net->d_wamp) { (void)hipFree(net->d_wamp); net->d_wamp = nullptr; }     // (the depth-1 fragments: never read)
-    if (st == NAQS_OK && net->d_wph) { (void)hipFree(net->d_wph); net->d_wph = nullptr; }
-    if (st == NAQS_OK && hipMalloc((void **)&net->d_wdeep, (size_t)doff * sizeof(float)) != hipSuccess) st = NAQS_ERR_NOMEM;
-    if (st == NAQS_OK && hipMalloc((void **)&net->d_wph, (size_t)poff * sizeof(float)) != hipSuccess) st = NAQS_ERR_NOMEM;
-    if (st != NAQS_OK) { naqs_net_destroy(net); return st; }
-    *out = net;
-    return NAQS_OK;
+    if (!deep_width_ok(Hp)) return NAQS_ERR_UNSUPPORTED;
+    if (cfg->amp_hidden > 0 && !deep_width_ok(cfg->amp_hidden)) return NAQS_ERR_UNSUPPORTED;
+    return net_build(cfg, naqs::Family::AGGREGATE, n_hidden, device, out);
 }
 
 NAQS_API int naqs_net_create_combined(const naqs_net_config_t *cfg, int device, naqs_net_t **out) {
     if (!cfg || !out) return NAQS_ERR_INVALID;
     *out = nullptr;
     if (cfg->aggregate_phase != 0) return NAQS_ERR_UNSUPPORTED;           // (the single-phase family only)
-    if (cfg->amp_hidden > 0 && ((cfg->amp_hidden & 15) || cfg->amp_hidden > 128)) return NAQS_ERR_UNSUPPORTED;
+    if (cfg->amp_hidden > 0 && !deep_width_ok(cfg->amp_hidden)) return NAQS_ERR_UNSUPPORTED;
     if ((cfg->use_phase_spin_sym != 0) != (cfg->use_amp_spin_sym != 0)) return NAQS_ERR_INVALID;      // (nade.py forces them equal)
-    // the per-pair machinery of the aggregate family (amplitude rows + fragments, a second set of raw blocks of the same width,
-    // no phase MLP), of which the combined handle uses the amplitude set and the last raw block
-    naqs_net_config_t c = *cfg;
-    c.aggregate_phase = 1;
-    c.n_phase_hidden = 1;
-    c.phase_hidden[0] = cfg->amp_hidden;
-    naqs_net_t *net = nullptr;
-    int st = naqs_net_create(&c, device, &net);
-    if (st != NAQS_OK) return st;
-    net->cfg = *cfg;
-    net->aggregate = false;
-    net->comb = true;
-    const NetDims &d = net->dims;
-    const int64_t nin = 2 * (d.P - 1), nph = net->dph.n_out_amp;
-    net->comb_amp = net->amp_params;
-    net->comb_head = d.Ha * nin + d.Ha + nph * d.Ha + nph;
-    net->n_params = net->comb_amp + nph * d.Ha + nph;
-    net->amp_params = net->n_params;                      // (no phase layers: every parameter belongs to the blocks)
-    net->ph_params = 0;
-    for (int64_t &o : net->ph_src_off) o = 0;
-    DeviceGuard guard;
-    st = guard.init(device);
-    if (st == NAQS_OK && hipMalloc((void **)&net->d_cflat, (size_t)(net->comb_amp + net->comb_head) * sizeof(float)) != hipSuccess)
-        st = NAQS_ERR_NOMEM;
-    if (st != NAQS_OK) { naqs_net_destroy(net); return st; }
-    *out = net;
-    return NAQS_OK;
+    return net_build(cfg, naqs::Family::COMBINED, 1, device, out);
 }
 
 NAQS_API int naqs_net_destroy(naqs_net_t *net) {
@@ -2143,11 +2105,11 @@ NAQS_API int naqs_net_destroy(naqs_net_t *net) {
     (void)guard.init(net->device);
     (void)net->prof.enable(0);
     (void)net->prof_samp.enable(0);
+    if (net->amp.w && net->amp.w != net->d_w) (void)hipFree(net->amp.w);      // (a set owns its copy unless it is d_w's rows)
+    if (net->ph.w) (void)hipFree(net->ph.w);
     if (net->d_w) (void)hipFree(net->d_w);
-    if (net->d_wph) (void)hipFree(net->d_wph);
     if (net->d_wh) (void)hipFree(net->d_wh);
     if (net->d_wamp) (void)hipFree(net->d_wamp);
-    if (net->d_wdeep) (void)hipFree(net->d_wdeep);
     if (net->d_cflat) (void)hipFree(net->d_cflat);
     if (net->d_cpart) (void)hipFree(net->d_cpart);
     if (net->d_scratch) (void)hipFree(net->d_scratch);
@@ -2188,48 +2150,36 @@ static int phase_rb_max(const NetDims &d, int fmt) {
     return (int)std::min<size_t>(fmt == 2 ? 4 : 3, (size_t)(155 * 1024) / phase_slab_bytes(d, fmt));
 }
 
-// deep amplitude blocks: their f32 copy (naqs_amp_deep.hpp) — what every deep kernel reads
-static int pack_deep(naqs_net *net, const float *flat_dev, hipStream_t s) {
-    const NetDims &d = net->dims;
-    const int64_t biggest = naqs::deep_pair_floats(d.Ha, d.n_out_amp, net->amp_depth, d.P - 1);
+// deep blocks: the set's f32 copy (naqs_amp_deep.hpp) — what every deep kernel reads
+static int pack_deep(const naqs::BlockSet &b, const float *flat_dev, hipStream_t s) {
+    const NetDims &d = b.d;
+    const int64_t biggest = naqs::deep_pair_floats(d.Ha, d.n_out_amp, b.depth, d.P - 1);
     NAQS_KLAUNCH(deep_pack_kernel, dim3((unsigned)std::min<int64_t>(64, (biggest + 255) / 256), (unsigned)d.P), dim3(256), 0, s, flat_dev,
-                       naqs::deep_amp(net), d.Ha, d.n_out_amp, net->d_wdeep);
+                       naqs::deep_blocks(b), d.Ha, d.n_out_amp, b.w);
     HIP_TRY(hipGetLastError());
     return NAQS_OK;
 }
 
-// ... and the deep phase blocks of an aggregate-phase handle (naqs_net_create_agg_layers) into d_wph, the same way
-static int pack_deep_phase(naqs_net *net, const float *flat_dev, hipStream_t s) {
-    const NetDims &q = net->dph;
-    const int64_t biggest = naqs::deep_pair_floats(q.Ha, q.n_out_amp, net->amp_depth, q.P - 1);
-    NAQS_KLAUNCH(deep_pack_kernel, dim3((unsigned)std::min<int64_t>(64, (biggest + 255) / 256), (unsigned)q.P), dim3(256), 0, s, flat_dev,
-                       naqs::deep_phase(net), q.Ha, q.n_out_amp, net->d_wph);
-    HIP_TRY(hipGetLastError());
-    return NAQS_OK;
-}
-
-static int pack_blocks(const NetDims &d, const int64_t *src_off, float *dst, const float *flat_dev, hipStream_t s) {
-    AmpSrcOff so;
-    for (int n = 0; n < MAXP; ++n) so.off[n] = src_off[n];
-    const int total_max = d.Ha * ((2 * (d.P - 1) + 1 + 5 + 3) & ~3) + 8;
-    NAQS_KLAUNCH(pack_amp_kernel, dim3((total_max + 255) / 256, d.P), dim3(256), 0, s, flat_dev, d, so, dst);
+// depth-1 blocks: the set's packed rows
+static int pack_blocks(const naqs::BlockSet &b, const float *flat_dev, hipStream_t s) {
+    const NetDims &d = b.d;
+    const int total_max = naqs::amp_block_floats(d.Ha, 2 * (d.P - 1));
+    NAQS_KLAUNCH(pack_amp_kernel, dim3((total_max + 255) / 256, d.P), dim3(256), 0, s, flat_dev, d, naqs::block_src<AmpSrcOff>(b), b.w);
     HIP_TRY(hipGetLastError());
     return NAQS_OK;
 }
 static int pack_amp_blocks(naqs_net_t *net, const float *flat_dev, hipStream_t s) {
     net->wamp_fresh = false;
-    return pack_blocks(net->dims, net->amp_src_off, net->d_w, flat_dev, s);
+    return pack_blocks(net->amp, flat_dev, s);
 }
 // rows + fragments of the amplitude blocks in one launch (naqs_net_set_amp_weights)
 static int pack_amp_both(naqs_net_t *net, const float *flat_dev, hipStream_t s) {
     if (!net->d_wamp) return pack_amp_blocks(net, flat_dev, s);
-    const NetDims &d = net->dims;
-    AmpSrcOff so;
-    for (int n = 0; n < MAXP; ++n) so.off[n] = net->amp_src_off[n];
-    const int frag = ((d.Ha >> 4) + (d.Ha >> 5)) * 512;
-    const int total_max = std::max(d.Ha * ((2 * (d.P - 1) + 1 + 5 + 3) & ~3) + 8, frag);
+    const NetDims &d = net->amp.d;
+    const int total_max = std::max(naqs::amp_block_floats(d.Ha, 2 * (d.P - 1)), naqs::amp_frag_plane_elems(d.Ha));
     net->wamp_fresh = false;
-    NAQS_KLAUNCH(pack_amp_both_kernel, dim3((total_max + 255) / 256, d.P, 2), dim3(256), 0, s, flat_dev, d, so, net->d_w, net->d_wamp);
+    NAQS_KLAUNCH(pack_amp_both_kernel, dim3((total_max + 255) / 256, d.P, 2), dim3(256), 0, s, flat_dev, d, naqs::block_src<AmpSrcOff>(net->amp),
+                       net->amp.w, net->d_wamp);
     HIP_TRY(hipGetLastError());
     net->wamp_fresh = true;
     return NAQS_OK;
@@ -2237,40 +2187,61 @@ static int pack_amp_both(naqs_net_t *net, const float *flat_dev, hipStream_t s) 
 // the amplitude blocks as MFMA fragments alone (the aggregate-phase family's unmerged path)
 static int pack_amp_fragments(naqs_net_t *net, const float *flat_dev, hipStream_t s) {
     if (!net->d_wamp) return NAQS_OK;
-    const NetDims &d = net->dims;
-    AmpSrcOff so;
-    for (int n = 0; n < MAXP; ++n) so.off[n] = net->amp_src_off[n];
-    const int frag = ((d.Ha >> 4) + (d.Ha >> 5)) * 512;          // elements of one plane
-    NAQS_KLAUNCH(pack_amp_mfma_kernel, dim3((frag + 255) / 256, d.P), dim3(256), 0, s, flat_dev, d, so, net->d_wamp);
+    const NetDims &d = net->amp.d;
+    NAQS_KLAUNCH(pack_amp_mfma_kernel, dim3((naqs::amp_frag_plane_elems(d.Ha) + 255) / 256, d.P), dim3(256), 0, s, flat_dev, d,
+                       naqs::block_src<AmpSrcOff>(net->amp), net->d_wamp);
     HIP_TRY(hipGetLastError());
     net->wamp_fresh = true;
     return NAQS_OK;
 }
 
-// combined blocks: the whole re-pack — the flat parameters re-laid out into d_cflat, then the amplitude rows and fragments (byte for
+// COMBINED: the whole re-pack — the flat parameters re-laid out into d_cflat, then the amplitude rows and fragments (byte for
 // byte a plain handle's of the same amplitude rows) and the phase head's rows in one launch
 static int pack_comb(naqs_net_t *net, const float *flat_dev, hipStream_t s) {
-    const NetDims &d = net->dims;
+    const NetDims &d = net->amp.d;
     const naqs::CombLayout c = naqs::comb_layout(net);
     NAQS_KLAUNCH(comb_split_kernel, dim3((unsigned)std::min<int64_t>(256, (c.total + 255) / 256)), dim3(256), 0, s, flat_dev, c, net->d_cflat);
     HIP_TRY(hipGetLastError());
-    AmpSrcOff so0, so1;
-    for (int n = 0; n < MAXP; ++n) { so0.off[n] = net->amp_src_off[n]; so1.off[n] = 0; }
+    AmpSrcOff so1 = naqs::block_src<AmpSrcOff>(net->ph);      // (all 0: the head's one block sits behind the amplitude blocks in d_cflat)
     so1.off[d.P - 1] = net->comb_amp;
-    const int frag = ((d.Ha >> 4) + (d.Ha >> 5)) * 512;
-    const int total_max = std::max(d.Ha * ((2 * (d.P - 1) + 1 + 5 + 3) & ~3) + 8, net->d_wamp ? frag : 0);
+    const int total_max = std::max(naqs::amp_block_floats(d.Ha, 2 * (d.P - 1)), net->d_wamp ? naqs::amp_frag_plane_elems(d.Ha) : 0);
     net->wamp_fresh = false;
-    NAQS_KLAUNCH(comb_pack_kernel, dim3((total_max + 255) / 256, 2 * d.P + 1), dim3(256), 0, s, net->d_cflat, d, so0, net->d_w, net->d_wamp,
-                       net->dph, so1, net->d_wph);
+    NAQS_KLAUNCH(comb_pack_kernel, dim3((total_max + 255) / 256, 2 * d.P + 1), dim3(256), 0, s, net->d_cflat, d, naqs::block_src<AmpSrcOff>(net->amp),
+                       net->amp.w, net->d_wamp, net->ph.d, so1, net->ph.w);
     HIP_TRY(hipGetLastError());
     net->wamp_fresh = net->d_wamp != nullptr;
-    net->have_weights = net->have_amp_weights = net->have_wb = true;
     return NAQS_OK;
 }
 
+// AGGREGATE: both sets of blocks — deep: the two f32 copies, the amplitude set's first; depth 1: the phase blocks in the amplitude
+// rows' layout, in one launch with the amplitude rows and fragments (NAQS_AGG_MERGE & 4) or one launch each
+static int pack_aggregate(naqs_net_t *net, const float *flat_dev, hipStream_t s) {
+    const NetDims &d = net->amp.d;
+    int st;
+    if (net->amp.deep()) {
+        st = pack_deep(net->amp, flat_dev, s);
+        if (st != NAQS_OK) return st;
+        return pack_deep(net->ph, flat_dev, s);
+    }
+    if (d.P == net->ph.d.P && (naqs::env_int("NAQS_AGG_MERGE", 7) & 4)) {
+        const int total_max = std::max(naqs::amp_block_floats(std::max(d.Ha, net->ph.d.Ha), 2 * (d.P - 1)), net->d_wamp ? naqs::amp_frag_plane_elems(d.Ha) : 0);
+        net->wamp_fresh = false;
+        NAQS_KLAUNCH(pack_amp2_kernel, dim3((total_max + 255) / 256, d.P, net->d_wamp ? 3 : 2), dim3(256), 0, s, flat_dev, d,
+                           naqs::block_src<AmpSrcOff>(net->amp), net->amp.w, net->ph.d, naqs::block_src<AmpSrcOff>(net->ph), net->ph.w, net->d_wamp);
+        HIP_TRY(hipGetLastError());
+        net->wamp_fresh = net->d_wamp != nullptr;
+        return NAQS_OK;
+    }
+    st = pack_amp_blocks(net, flat_dev, s);
+    if (st != NAQS_OK) return st;
+    st = pack_blocks(net->ph, flat_dev, s);
+    if (st != NAQS_OK) return st;
+    return pack_amp_fragments(net, flat_dev, s);
+}
+
 NAQS_API int naqs_net_set_amp_weights(naqs_net_t *net, const float *flat_dev, int64_t count, void *stream) {
-    if (net && net->comb) return naqs_net_set_weights(net, flat_dev, count, stream);     // (every parameter is a block's)
-    if (!net || !flat_dev || (count != net->n_params && count != net->amp_params)) return NAQS_ERR_INVALID;
+    if (net && net->family == naqs::Family::COMBINED) return naqs_net_set_weights(net, flat_dev, count, stream);     // (every parameter is a block's)
+    if (!net || !flat_dev || (count != net->n_params && count != net->amp.n_params)) return NAQS_ERR_INVALID;
     DeviceGuard guard;
     int st = guard.init(net->device);
     if (st != NAQS_OK) return st;
@@ -2282,8 +2253,8 @@ NAQS_API int naqs_net_set_amp_weights(naqs_net_t *net, const float *flat_dev, in
     // rows AND fragments: the sampler picks the matrix-core form of the block MLPs whenever the fragments are current, and the
     // two forms round differently — the same (parameters, seed) must not draw differently depending on which call packed last
     // (deep blocks: their f32 copy is the only form)
-    st = net->amp_depth > 1 ? pack_deep(net, flat_dev, reinterpret_cast<hipStream_t>(stream))
-                            : pack_amp_both(net, flat_dev, reinterpret_cast<hipStream_t>(stream));
+    st = net->amp.deep() ? pack_deep(net->amp, flat_dev, reinterpret_cast<hipStream_t>(stream))
+                         : pack_amp_both(net, flat_dev, reinterpret_cast<hipStream_t>(stream));
     if (st != NAQS_OK) return st;
     net->have_amp_weights = true;
     return NAQS_OK;
@@ -2300,10 +2271,10 @@ NAQS_API int naqs_net_set_amp_weights(naqs_net_t *net, const float *flat_dev, in
 // jobs in order first (net_flush_pack).
 enum PackMode { PACK_ALL = 0, PACK_AMP = 1, PACK_PHASE = 2, PACK_TAKE = 3, PACK_DEFER = 4 };
 static int pack_single_phase(naqs_net *net, const float *flat_dev, hipStream_t s, PackMode mode, naqs::PackPhaseArgs *take, const int head_pairs = 0) {
-    const NetDims &d = net->dims;
+    const NetDims &d = net->amp.d;
     PhasePackJobs jobs{};
-    int biggest = d.Ha * ((2 * (d.P - 1) + 1 + 5 + 3) & ~3) + 8;                 // an amplitude block's packed rows
-    const int amp_biggest = std::max(biggest, (d.Ha / 16 + d.Ha / 32) * 512);
+    int biggest = naqs::amp_block_floats(d.Ha, 2 * (d.P - 1));                         // an amplitude block's packed rows
+    const int amp_biggest = std::max(biggest, naqs::amp_frag_plane_elems(d.Ha));
     for (int l = 0; l < d.n_lin; ++l) {
         jobs.src_off[l] = net->phase_src_off[(size_t)l];
         jobs.K[l] = net->phase_K[(size_t)l];
@@ -2317,14 +2288,13 @@ static int pack_single_phase(naqs_net *net, const float *flat_dev, hipStream_t s
     int st = naqs::net_backward_pack_jobs(net, &wb);
     if (st != NAQS_OK) return st;
     for (int i = 0; i < wb.n; ++i) biggest = std::max(biggest, wb.Np[i] * wb.Kp[i]);
-    AmpSrcOff so;
-    for (int n = 0; n < MAXP; ++n) so.off[n] = net->amp_src_off[n];
+    const AmpSrcOff so = naqs::block_src<AmpSrcOff>(net->amp);
     const int gx = std::min(256, (biggest + 255) / 256);
     const int gy_amp = d.P + (net->d_wamp ? d.P : 0), gy_phase = d.n_lin + wb.n;
     naqs::PhaseRaw *raw = net->d_raw;
     if (mode == PACK_DEFER && (fmt != 2 || net->d_wamp == nullptr || net->amp_head_packed <= 0)) mode = PACK_AMP;      // (nothing to host the amplitude share with)
-    if (net->amp_depth > 1 && (mode == PACK_ALL || mode == PACK_AMP)) {      // (deep blocks: d_wamp is null, so no PACK_DEFER)
-        st = pack_deep(net, flat_dev, s);
+    if (net->amp.deep() && (mode == PACK_ALL || mode == PACK_AMP)) {         // (deep blocks: d_wamp is null, so no PACK_DEFER)
+        st = pack_deep(net->amp, flat_dev, s);
         if (st != NAQS_OK) return st;
     }
     if (mode == PACK_ALL || mode == PACK_AMP || mode == PACK_DEFER) {
@@ -2351,7 +2321,7 @@ static int pack_single_phase(naqs_net *net, const float *flat_dev, hipStream_t s
         net->pack_pending = nullptr;
         net->pack_pending_amp = false;
     } else if (mode == PACK_AMP) {
-        if (net->amp_depth == 1) {                         // (deep blocks: pack_deep above is their whole amplitude share)
+        if (!net->amp.deep()) {                            // (deep blocks: pack_deep above is their whole amplitude share)
             NAQS_KLAUNCH(pack_net_kernel, dim3(std::min(256, (amp_biggest + 255) / 256), gy_amp), dim3(256), 0, s, flat_dev, d, so, jobs, wb,
                                net->d_w, net->d_wh, net->d_wamp, with_f32, fmt, raw, net->d_scales, 0, 0u, net->ctl);
             HIP_TRY(hipGetLastError());
@@ -2377,8 +2347,8 @@ static int pack_single_phase(naqs_net *net, const float *flat_dev, hipStream_t s
         take->n_wgs = d.n_lin * naqs::BOUNDS_WG + wb.n * gx + d.n_lin * take->gxl;
         if (net->pack_pending_amp) {                       // the amplitude share rides along, in front (naqs_pack.hpp)
             take->amp = 1; take->so = so; take->wamp = net->d_wamp; take->head_pairs = std::min(head_pairs, d.P);
-            take->gxa = std::max(1, ((d.Ha * ((2 * (d.P - 1) + 1 + 5 + 3) & ~3) + 8) + 255) / 256);
-            take->gxf = std::max(1, ((d.Ha / 16 + d.Ha / 32) * 512 + 255) / 256);
+            take->gxa = std::max(1, (naqs::amp_block_floats(d.Ha, 2 * (d.P - 1)) + 255) / 256);
+            take->gxf = std::max(1, (naqs::amp_frag_plane_elems(d.Ha) + 255) / 256);
             take->n_amp_wgs = d.P * take->gxa + (d.P - take->head_pairs) * take->gxf;
             take->n_wgs += take->n_amp_wgs;
         }
@@ -2452,53 +2422,25 @@ NAQS_API int naqs_net_set_weights(naqs_net_t *net, const float *flat_dev, int64_
     int st = guard.init(net->device);
     if (st != NAQS_OK) return st;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const NetDims &d = net->dims;
     net->have_weights = net->have_amp_weights = net->have_wb = false;
     net->pack_pending = nullptr;                          // (whatever was pending is superseded by this re-pack)
     net->pack_pending_amp = false;
     if (net->overlap_next_pack != 2) net->amp_head_packed = 0;      // (only naqs_vmc_step's update packs leading pairs itself)
-    if (net->comb) return pack_comb(net, flat_dev, s);      // (nothing is left pending: no launch hosts a share of it)
-    if (net->aggregate && net->amp_depth > 1) {             // deep blocks: both f32 copies, the amplitude set's first
-        st = pack_deep(net, flat_dev, s);
-        if (st != NAQS_OK) return st;
-        st = pack_deep_phase(net, flat_dev, s);
-        if (st != NAQS_OK) return st;
-        net->have_weights = net->have_amp_weights = net->have_wb = true;
-        return NAQS_OK;
+    switch (net->family) {                                  // (only the single-phase re-pack can leave a share pending for a launch to host)
+        case naqs::Family::COMBINED: st = pack_comb(net, flat_dev, s); break;
+        case naqs::Family::AGGREGATE: st = pack_aggregate(net, flat_dev, s); break;
+        case naqs::Family::SINGLE_PHASE:
+            st = pack_single_phase(net, flat_dev, s, net->overlap_next_pack == 2 ? PACK_DEFER : (net->overlap_next_pack ? PACK_AMP : PACK_ALL), nullptr);
+            break;
     }
-    if (net->aggregate) {                                   // the phase blocks in the amplitude rows' layout; nothing else to pack
-        if (net->dims.P == net->dph.P && (naqs::env_int("NAQS_AGG_MERGE", 7) & 4)) {
-            AmpSrcOff so0, so1;
-            for (int n = 0; n < MAXP; ++n) { so0.off[n] = net->amp_src_off[n]; so1.off[n] = net->ph_src_off[n]; }
-            const int frag = ((d.Ha >> 4) + (d.Ha >> 5)) * 512;
-            const int total_max = std::max(std::max(d.Ha, net->dph.Ha) * ((2 * (d.P - 1) + 1 + 5 + 3) & ~3) + 8, net->d_wamp ? frag : 0);
-            net->wamp_fresh = false;
-            NAQS_KLAUNCH(pack_amp2_kernel, dim3((total_max + 255) / 256, d.P, net->d_wamp ? 3 : 2), dim3(256), 0, s, flat_dev, d, so0, net->d_w,
-                               net->dph, so1, net->d_wph, net->d_wamp);
-            HIP_TRY(hipGetLastError());
-            net->wamp_fresh = net->d_wamp != nullptr;
-            net->have_weights = net->have_amp_weights = net->have_wb = true;
-            return NAQS_OK;
-        } else {
-            st = pack_amp_blocks(net, flat_dev, s);
-            if (st != NAQS_OK) return st;
-            st = pack_blocks(net->dph, net->ph_src_off, net->d_wph, flat_dev, s);
-            if (st != NAQS_OK) return st;
-        }
-        st = pack_amp_fragments(net, flat_dev, s);
-        if (st != NAQS_OK) return st;
-        net->have_weights = net->have_amp_weights = net->have_wb = true;
-        return NAQS_OK;
-    }
-    st = pack_single_phase(net, flat_dev, s, net->overlap_next_pack == 2 ? PACK_DEFER : (net->overlap_next_pack ? PACK_AMP : PACK_ALL), nullptr);
     if (st != NAQS_OK) return st;
-    net->have_weights = net->have_amp_weights = true;
+    net->have_weights = net->have_amp_weights = net->have_wb = true;      // (have_wb: the single-phase re-pack has set it in these modes)
     return NAQS_OK;
 }
 
 static int launch_amp_kernel(const NetDims &d, const float *w, int64_t M, const uint64_t *keys_dev, float *scratch,
                              const ElocFeed &feed, int raw, hipStream_t s) {
-    const size_t amp_lds = ((size_t)d.Ha * ((2 * (d.P - 1) + 1 + 5 + 3) & ~3) + 8) * sizeof(float);
+    const size_t amp_lds = (size_t)naqs::amp_block_floats(d.Ha, 2 * (d.P - 1)) * sizeof(float);
     if (amp_lds > 64 * 1024) return NAQS_ERR_UNSUPPORTED;
     NAQS_KLAUNCH(amp_kernel, dim3((unsigned)((M + AMP_TILES * WAVE - 1) / (AMP_TILES * WAVE)), (unsigned)d.P), dim3(AMP_TILES * AMP_SPLIT * WAVE), amp_lds, s, d, w, M,
                        keys_dev, scratch, feed, raw);
@@ -2507,7 +2449,7 @@ static int launch_amp_kernel(const NetDims &d, const float *w, int64_t M, const 
 }
 
 int naqs::net_amp_forward(naqs_net *net, int64_t M, const uint64_t *keys_dev, hipStream_t s, const ElocFeed *feed, bool launch) {
-    const NetDims &d = net->dims;
+    const NetDims &d = net->amp.d;
     if (M >= (1ll << 31)) return NAQS_ERR_UNSUPPORTED;
     if (M > net->cap_M) {
         HIP_TRY(hipDeviceSynchronize());
@@ -2515,25 +2457,23 @@ int naqs::net_amp_forward(naqs_net *net, int64_t M, const uint64_t *keys_dev, hi
         net->d_scratch = nullptr; net->cap_M = 0;
         const int64_t cap = std::max<int64_t>(1024, M + M / 4);
         // [P][cap] conditional log-amplitudes (+ [P][cap] phases of the per-pair phase blocks, or the phase head's in row P - 1)
-        HIP_TRY(hipMalloc((void **)&net->d_scratch, (size_t)cap * d.P * (net->aggregate || net->comb ? 2 : 1) * sizeof(float)));
+        HIP_TRY(hipMalloc((void **)&net->d_scratch, (size_t)cap * d.P * (naqs::has_second_set(net) ? 2 : 1) * sizeof(float)));
         net->cap_M = cap;
     }
     if (!launch) return NAQS_OK;
     const ElocFeed none{};
-    if (net->amp_depth > 1) {
+    if (net->amp.deep()) {
         const int CT = d.Ha >> 4;
         const int64_t items = (M + 15) / 16 * d.P;
         const unsigned grid = (unsigned)((items + DEEPK_WAVES - 1) / DEEPK_WAVES);
-        const naqs::DeepAmp da = naqs::deep_amp(net);
-        std::snprintf(net->last_amp, sizeof(net->last_amp), "amp_deep_kernel<%d, L=%d>", CT, net->amp_depth);
-        switch (CT) {
-#define NAQS_DEEP(C) case C: NAQS_KLAUNCH(amp_deep_kernel<C>, dim3(grid), dim3(DEEPK_WAVES * 64), 0, s, d, net->d_wdeep, da, M, keys_dev, net->d_scratch, feed ? *feed : none); break;
-            NAQS_DEEP(1) NAQS_DEEP(2) NAQS_DEEP(3) NAQS_DEEP(4) NAQS_DEEP(5) NAQS_DEEP(6) NAQS_DEEP(7) NAQS_DEEP(8)
-#undef NAQS_DEEP
-            default: return NAQS_ERR_UNSUPPORTED;
-        }
-        HIP_TRY(hipGetLastError());
-        return NAQS_OK;
+        const naqs::DeepAmp da = naqs::deep_blocks(net->amp);
+        std::snprintf(net->last_amp, sizeof(net->last_amp), "amp_deep_kernel<%d, L=%d>", CT, net->amp.depth);
+        return naqs::dispatch_width(CT, [&](auto c) -> int {
+            NAQS_KLAUNCH(amp_deep_kernel<decltype(c)::value>, dim3(grid), dim3(DEEPK_WAVES * 64), 0, s, d, net->amp.w, da, M, keys_dev, net->d_scratch,
+                         feed ? *feed : none);
+            HIP_TRY(hipGetLastError());
+            return NAQS_OK;
+        });
     }
     if (net->d_wamp != nullptr && net->wamp_fresh && naqs::env_int("NAQS_AMP_MODE", 1) != 0) {      // matrix-core form (0: the VALU amp_kernel)
         const int64_t waves = (M + AMPK_TG * 16 - 1) / (AMPK_TG * 16) * d.P;
@@ -2547,46 +2487,44 @@ int naqs::net_amp_forward(naqs_net *net, int64_t M, const uint64_t *keys_dev, hi
         return NAQS_OK;
     }
     std::snprintf(net->last_amp, sizeof(net->last_amp), "amp_kernel");
-    return launch_amp_kernel(d, net->d_w, M, keys_dev, net->d_scratch, feed ? *feed : none, 0, s);
+    return launch_amp_kernel(d, net->amp.w, M, keys_dev, net->d_scratch, feed ? *feed : none, 0, s);
 }
 
 // aggregate_phase with deep blocks (naqs_net_create_agg_layers): both sets in agg_deep_kernel when Ha == Hp (NAQS_AGG_MERGE & 1),
 // else amp_deep_kernel (net_amp_forward, which also feeds E_loc the keys) and amp_deep_raw_kernel; then the sums
 static int agg_deep_logpsi(naqs_net *net, int64_t M, const uint64_t *keys_dev, float *logpsi_dev, hipStream_t s, const ElocFeed &feed) {
-    const NetDims &d0 = net->dims, &d1 = net->dph;
+    const NetDims &d0 = net->amp.d, &d1 = net->ph.d;
     const bool prof = net->prof.armed();
     if (prof) { int stp = net->prof.begin(s); if (stp != NAQS_OK) return stp; }
     int st = naqs::net_amp_forward(net, M, keys_dev, s, nullptr, /*launch=*/false);          // (the scratch only)
     if (st != NAQS_OK) return st;
     float *s_ph = net->d_scratch + (size_t)d0.P * net->cap_M;
-    const naqs::DeepAmp da0 = naqs::deep_amp(net), da1 = naqs::deep_phase(net);
+    const naqs::DeepAmp da0 = naqs::deep_blocks(net->amp), da1 = naqs::deep_blocks(net->ph);
     const int64_t set_items = (M + 15) / 16 * d0.P;
     const int CT0 = d0.Ha >> 4, CT1 = d1.Ha >> 4;
     if (CT0 < 1 || CT0 > 8 || CT1 < 1 || CT1 > 8 || d0.P != d1.P) return NAQS_ERR_UNSUPPORTED;
     if (CT0 == CT1 && (naqs::env_int("NAQS_AGG_MERGE", 7) & 1)) {
         const unsigned grid = (unsigned)((2 * set_items + DEEPK_WAVES - 1) / DEEPK_WAVES);
-        switch (CT0) {
-#define NAQS_DEEP(C) case C: NAQS_KLAUNCH(agg_deep_kernel<C>, dim3(grid), dim3(DEEPK_WAVES * 64), 0, s, d0, net->d_wdeep, da0, net->d_scratch, feed, \
-                                          d1, net->d_wph, da1, s_ph, M, keys_dev); break;
-            NAQS_DEEP(1) NAQS_DEEP(2) NAQS_DEEP(3) NAQS_DEEP(4) NAQS_DEEP(5) NAQS_DEEP(6) NAQS_DEEP(7) NAQS_DEEP(8)
-#undef NAQS_DEEP
-            default: return NAQS_ERR_UNSUPPORTED;
-        }
-        HIP_TRY(hipGetLastError());
-        std::snprintf(net->last_kernel, sizeof(net->last_kernel), "agg_deep_kernel<%d, L=%d> + agg_finish_kernel", CT0, net->amp_depth);
+        st = naqs::dispatch_width(CT0, [&](auto c) -> int {
+            NAQS_KLAUNCH(agg_deep_kernel<decltype(c)::value>, dim3(grid), dim3(DEEPK_WAVES * 64), 0, s, d0, net->amp.w, da0, net->d_scratch, feed,
+                         d1, net->ph.w, da1, s_ph, M, keys_dev);
+            HIP_TRY(hipGetLastError());
+            return NAQS_OK;
+        });
+        if (st != NAQS_OK) return st;
+        std::snprintf(net->last_kernel, sizeof(net->last_kernel), "agg_deep_kernel<%d, L=%d> + agg_finish_kernel", CT0, net->amp.depth);
     } else {
         st = naqs::net_amp_forward(net, M, keys_dev, s, &feed);
         if (st != NAQS_OK) return st;
         const unsigned grid = (unsigned)((set_items + DEEPK_WAVES - 1) / DEEPK_WAVES);
-        switch (CT1) {
-#define NAQS_DEEP(C) case C: NAQS_KLAUNCH(amp_deep_raw_kernel<C>, dim3(grid), dim3(DEEPK_WAVES * 64), 0, s, d1, net->d_wph, da1, M, keys_dev, s_ph); break;
-            NAQS_DEEP(1) NAQS_DEEP(2) NAQS_DEEP(3) NAQS_DEEP(4) NAQS_DEEP(5) NAQS_DEEP(6) NAQS_DEEP(7) NAQS_DEEP(8)
-#undef NAQS_DEEP
-            default: return NAQS_ERR_UNSUPPORTED;
-        }
-        HIP_TRY(hipGetLastError());
+        st = naqs::dispatch_width(CT1, [&](auto c) -> int {
+            NAQS_KLAUNCH(amp_deep_raw_kernel<decltype(c)::value>, dim3(grid), dim3(DEEPK_WAVES * 64), 0, s, d1, net->ph.w, da1, M, keys_dev, s_ph);
+            HIP_TRY(hipGetLastError());
+            return NAQS_OK;
+        });
+        if (st != NAQS_OK) return st;
         std::snprintf(net->last_kernel, sizeof(net->last_kernel), "%s + amp_deep_raw_kernel<%d, L=%d> + agg_finish_kernel", net->last_amp, CT1,
-                      net->amp_depth);
+                      net->amp.depth);
     }
     NAQS_KLAUNCH(agg_finish_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, d0.P, M, net->d_scratch, s_ph,
                        reinterpret_cast<float2 *>(logpsi_dev), feed);
@@ -2602,34 +2540,34 @@ static int agg_logpsi(naqs_net *net, int64_t M, const uint64_t *keys_dev, float 
     const bool prof = net->prof.armed();
     int st;
     float *s_ph;
-    if (!mfma_amp && !prof && net->dims.P == net->dph.P && (naqs::env_int("NAQS_AGG_MERGE", 7) & 1)) {
+    if (!mfma_amp && !prof && net->amp.d.P == net->ph.d.P && (naqs::env_int("NAQS_AGG_MERGE", 7) & 1)) {
         st = naqs::net_amp_forward(net, M, keys_dev, s, nullptr, /*launch=*/false);          // (the scratch only)
         if (st != NAQS_OK) return st;
-        s_ph = net->d_scratch + (size_t)net->dims.P * net->cap_M;
-        const NetDims &d0 = net->dims, &d1 = net->dph;
-        const size_t lds = ((size_t)std::max(d0.Ha, d1.Ha) * ((2 * (d0.P - 1) + 1 + 5 + 3) & ~3) + 8) * sizeof(float);
+        s_ph = net->d_scratch + (size_t)net->amp.d.P * net->cap_M;
+        const NetDims &d0 = net->amp.d, &d1 = net->ph.d;
+        const size_t lds = (size_t)naqs::amp_block_floats(std::max(d0.Ha, d1.Ha), 2 * (d0.P - 1)) * sizeof(float);
         if (lds > 64 * 1024) return NAQS_ERR_UNSUPPORTED;
         NAQS_KLAUNCH(amp2_kernel, dim3((unsigned)((M + AMP_TILES * WAVE - 1) / (AMP_TILES * WAVE)), (unsigned)d0.P, 2),
-                           dim3(AMP_TILES * AMP_SPLIT * WAVE), lds, s, d0, net->d_w, net->d_scratch, feed, d1, net->d_wph, s_ph, M, keys_dev);
+                           dim3(AMP_TILES * AMP_SPLIT * WAVE), lds, s, d0, net->amp.w, net->d_scratch, feed, d1, net->ph.w, s_ph, M, keys_dev);
         HIP_TRY(hipGetLastError());
         std::snprintf(net->last_kernel, sizeof(net->last_kernel), "amp2_kernel + agg_finish_kernel");
     } else {
         if (mfma_amp) st = naqs::net_amp_forward(net, M, keys_dev, s, &feed);
         else {                                             // the VALU form, like the merged launch (same numbers)
             st = naqs::net_amp_forward(net, M, keys_dev, s, nullptr, /*launch=*/false);
-            if (st == NAQS_OK) st = launch_amp_kernel(net->dims, net->d_w, M, keys_dev, net->d_scratch, feed, 0, s);
+            if (st == NAQS_OK) st = launch_amp_kernel(net->amp.d, net->amp.w, M, keys_dev, net->d_scratch, feed, 0, s);
             std::snprintf(net->last_amp, sizeof(net->last_amp), "amp_kernel");
         }
         if (st != NAQS_OK) return st;
         std::snprintf(net->last_kernel, sizeof(net->last_kernel), "%s + amp_kernel(raw) + agg_finish_kernel", net->last_amp);
-        s_ph = net->d_scratch + (size_t)net->dims.P * net->cap_M;
+        s_ph = net->d_scratch + (size_t)net->amp.d.P * net->cap_M;
         const ElocFeed none{};
         if (prof) { st = net->prof.begin(s); if (st != NAQS_OK) return st; }
-        st = launch_amp_kernel(net->dph, net->d_wph, M, keys_dev, s_ph, none, 1, s);
+        st = launch_amp_kernel(net->ph.d, net->ph.w, M, keys_dev, s_ph, none, 1, s);
         if (st != NAQS_OK) return st;
         if (prof) { st = net->prof.end(s); if (st != NAQS_OK) return st; }
     }
-    NAQS_KLAUNCH(agg_finish_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, net->dims.P, M, net->d_scratch, s_ph,
+    NAQS_KLAUNCH(agg_finish_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, net->amp.d.P, M, net->d_scratch, s_ph,
                        reinterpret_cast<float2 *>(logpsi_dev), feed);
     HIP_TRY(hipGetLastError());
     return NAQS_OK;
@@ -2637,16 +2575,16 @@ static int agg_logpsi(naqs_net *net, int64_t M, const uint64_t *keys_dev, float 
 
 // combined amplitude-phase blocks: the amplitude launch net_amp_forward picks (it also feeds E_loc the keys), the phase head, the sums
 static int comb_logpsi(naqs_net *net, int64_t M, const uint64_t *keys_dev, float *logpsi_dev, hipStream_t s, const ElocFeed &feed) {
-    const NetDims &d = net->dims, &dh = net->dph;
+    const NetDims &d = net->amp.d, &dh = net->ph.d;
     const bool prof = net->prof.armed();
     if (prof) { int stp = net->prof.begin(s); if (stp != NAQS_OK) return stp; }
     int st = naqs::net_amp_forward(net, M, keys_dev, s, &feed);
     if (st != NAQS_OK) return st;
     float *s_head = net->d_scratch + (size_t)d.P * net->cap_M;        // (the head writes its row P - 1)
-    const size_t lds = ((size_t)dh.Ha * ((2 * (dh.P - 1) + 1 + 5 + 3) & ~3) + 8) * sizeof(float);
+    const size_t lds = (size_t)naqs::amp_block_floats(dh.Ha, 2 * (dh.P - 1)) * sizeof(float);
     if (lds > 64 * 1024) return NAQS_ERR_UNSUPPORTED;
     NAQS_KLAUNCH(comb_head_kernel, dim3((unsigned)((M + AMP_TILES * WAVE - 1) / (AMP_TILES * WAVE)), (unsigned)dh.P),
-                       dim3(AMP_TILES * AMP_SPLIT * WAVE), lds, s, dh, net->d_wph, M, keys_dev, s_head);
+                       dim3(AMP_TILES * AMP_SPLIT * WAVE), lds, s, dh, net->ph.w, M, keys_dev, s_head);
     HIP_TRY(hipGetLastError());
     NAQS_KLAUNCH(comb_finish_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, d.P, M, net->d_scratch,
                        s_head + (size_t)(dh.P - 1) * M, reinterpret_cast<float2 *>(logpsi_dev), feed);
@@ -2659,7 +2597,7 @@ static int comb_logpsi(naqs_net *net, int64_t M, const uint64_t *keys_dev, float
 // which form of the log-psi kernel M rows get (net_logpsi_impl; naqs::net_logpsi_form for callers that must know in advance)
 struct FormSel { bool ws = false, ws_split = false; int rb = 1; };
 static FormSel select_form(const naqs_net *net, const int64_t M, const int fmt, const size_t lds_h16, const int rb_max) {
-    const NetDims &d = net->dims;
+    const NetDims &d = net->amp.d;
     FormSel f;
     // wave-specialised form (phase_kernel_ws): the published shape in the f16x2 format, tiles of up to 48 rows
     const bool ws_shape = fmt == 2 && d.n_lin == 3 && d.N_pad[0] == PH_WAVES * CBT * 16 && d.N_pad[1] == WS_MW * WS_NCT * 16 &&
@@ -2688,8 +2626,8 @@ static FormSel select_form(const naqs_net *net, const int64_t M, const int fmt, 
 
 naqs::PhaseForm naqs::net_logpsi_form(const naqs_net *net, const int64_t M) {
     PhaseForm f;
-    const NetDims &d = net->dims;
-    if (net->aggregate || net->comb) return f;
+    const NetDims &d = net->amp.d;
+    if (!naqs::has_phase_mlp(net)) return f;
     const int fmt = phase_format(d);
     if (fmt == 0) return f;
     const size_t lds_h16 = phase_slab_bytes(d, fmt);
@@ -2713,13 +2651,16 @@ int naqs::net_logpsi_impl(naqs_net *net, int64_t M, const uint64_t *keys_dev, fl
     if (st != NAQS_OK) return st;
     st = naqs::poll_check(net->poll);                      // an earlier launch's device-side wait that gave up (naqs_poll.hpp)
     if (st != NAQS_OK) return st;
-    const NetDims &d = net->dims;
+    const NetDims &d = net->amp.d;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     st = naqs::net_flush_pack(net, s);                     // (the phase share of the last step's re-pack, if no launch hosted it)
     if (st != NAQS_OK) return st;
-    if (net->aggregate && net->amp_depth > 1) return agg_deep_logpsi(net, M, keys_dev, logpsi_dev, s, feed);
-    if (net->aggregate) return agg_logpsi(net, M, keys_dev, logpsi_dev, s, feed);
-    if (net->comb) return comb_logpsi(net, M, keys_dev, logpsi_dev, s, feed);
+    switch (net->family) {
+        case naqs::Family::AGGREGATE:
+            return net->amp.deep() ? agg_deep_logpsi(net, M, keys_dev, logpsi_dev, s, feed) : agg_logpsi(net, M, keys_dev, logpsi_dev, s, feed);
+        case naqs::Family::COMBINED: return comb_logpsi(net, M, keys_dev, logpsi_dev, s, feed);
+        case naqs::Family::SINGLE_PHASE: break;             // (below)
+    }
     const int fmt = phase_format(d);
     if (fmt != net->packed_fmt) return NAQS_ERR_INVALID;                       // NAQS_PHASE_MODE changed since naqs_net_set_weights
     const bool use_h = fmt != 0;
@@ -2924,7 +2865,7 @@ NAQS_API int naqs_net_prof_read(naqs_net_t *net, double *total_ms, int64_t *laun
 
 NAQS_API int naqs_net_last_kernel(const naqs_net_t *net, char *buf, int buf_len) {
     if (!net || !buf || buf_len <= 0) return NAQS_ERR_INVALID;
-    if (net->amp_depth > 1 && net->last_deep[0] != 0) std::snprintf(buf, (size_t)buf_len, "%s; %s", net->last_kernel, net->last_deep);
+    if (net->amp.deep() && net->last_deep[0] != 0) std::snprintf(buf, (size_t)buf_len, "%s; %s", net->last_kernel, net->last_deep);
     else std::snprintf(buf, (size_t)buf_len, "%s", net->last_kernel);
     return NAQS_OK;
 }

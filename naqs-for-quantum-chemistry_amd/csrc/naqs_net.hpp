@@ -38,6 +38,11 @@ struct NetDims {
     int32_t Kh_pad[MAXL], wh_off[MAXL];
     int32_t ldh;                       // LDS row stride of one activation plane (bf16 units)
 };
+// the geometry of amp_off's layout: floats of one packed row of `nin` inputs (a 16-byte multiple), floats of one packed block
+// of Ha such rows plus b2 [8], and the elements of one plane of a block's matrix-core fragments (naqs_amp_mfma.hpp)
+constexpr __host__ __device__ int amp_row_stride(int nin) { return (nin + 1 + 5 + 3) & ~3; }
+constexpr __host__ __device__ int amp_block_floats(int Ha, int nin) { return Ha * amp_row_stride(nin) + 8; }
+constexpr __host__ __device__ int amp_frag_plane_elems(int Ha) { return ((Ha >> 4) + (Ha >> 5)) * 512; }
 
 // f16x2 form of the phase MLP (phase_kernel_h<.., FMT = 2>): every f32 value v is carried as two f16 planes of s*v (s a power
 // of two per tensor: hi = f16(s v), lo = f16(s v - hi)), so that the values sit high in the f16 range and lo stays normal.
@@ -104,7 +109,7 @@ __device__ __forceinline__ void amp_partial(const NetDims &d, const float *__res
         }
     }
     const int nout = d.n_out_amp;
-    constexpr int S = (NIN + 1 + 5 + 3) & ~3;          // packed row: W1[j][:], b1[j], W2[:][j], padded to 16 bytes
+    constexpr int S = amp_row_stride(NIN);             // packed row: W1[j][:], b1[j], W2[:][j], padded to 16 bytes
     const float *rows = w;                             // this pair's rows, staged in LDS by the workgroup
 #pragma unroll 4
     for (int j = j0; j < j1; ++j) {
@@ -183,7 +188,7 @@ __device__ __forceinline__ void amp_conditional(const NetDims &d, int NB, const 
     for (int c = 0; c < 4; ++c) la[c] = ok[c] ? 0.5f * ((a4[c] - m) - ls) : -INFINITY;
 }
 
-// ---- combined amplitude-phase blocks (naqs_net_create_combined) ----
+// ---- combined amplitude-phase blocks (Family::COMBINED) ----
 // The flat parameters are the state_dict's: blocks 0 .. P-2 as in a plain handle, then the last block
 // W1 [Ha][nin] | b1 [Ha] | W2 [na + nph][Ha] | b2 [na + nph] (amplitude rows first).  The kernels read two re-laid-out copies:
 // the amplitude blocks in the plain layout (last block W1 | b1 | W2 [na][Ha] | b2 [na]) and the phase head
@@ -266,45 +271,56 @@ __device__ __forceinline__ void sample_finish_body(const SampleFinishJob &j, int
 }
 #endif
 
+// One set of per-pair blocks: what describes it, where its parameters sit in the flat source and the device copy its kernels read.
+struct BlockSet {
+    NetDims d{};
+    int depth = 1;                          // hidden layers of every block
+    bool raw = false;                       // the kernels take the realised outcome's output as it is (phase blocks, the phase head)
+    int64_t src_off[MAXP] = {};             // per pair: offset in the flat source
+    int64_t n_params = 0;                   // floats of the set in the flat source
+    float *w = nullptr;                     // depth 1: packed rows, pair n at d.amp_off[n]; depth 2..4: naqs_amp_deep.hpp's layout,
+    int64_t deep_off[MAXP] = {};            //   pair n at deep_off[n] (multiples of 4; deep_floats in all)
+    int64_t deep_floats = 0;
+    bool deep() const { return depth > 1; }
+};
+// per-pair source offsets as a kernel argument (naqs_pack.hpp: AmpSrcOff; naqs_amp_backward.hpp: AmpSrc, relative to the set's first)
+template <typename T>
+inline T block_src(const BlockSet &b, const bool relative = false) {
+    T so;
+    for (int n = 0; n < MAXP; ++n) so.off[n] = b.src_off[n] - (relative ? b.src_off[0] : 0);
+    return so;
+}
+
+// Which network a handle is.  The depth of the blocks is BlockSet::depth, not part of the tag.
+enum class Family {
+    SINGLE_PHASE,                           // amplitude blocks + one phase MLP on the first P - 1 pairs
+    AGGREGATE,                              // amplitude blocks + one raw phase block per pair (-aggregate_phase)
+    COMBINED,                               // amplitude blocks whose last output layer also carries the phase rows (-comb_amp_phase)
+};
+
 }  // namespace naqs
 
 struct naqs_net {
     int device = 0;
     naqs_net_config_t cfg{};
-    naqs::NetDims dims{};
+    naqs::Family family = naqs::Family::SINGLE_PHASE;
     int64_t n_params = 0;
-    int64_t amp_params = 0;                 // floats of all amplitude blocks in the flat source
-    int64_t amp_src_off[naqs::MAXP] = {};         // per pair: offset in the flat source
+    // the two sets of per-pair blocks.  amp: the amplitude blocks (amp.n_params: the floats naqs_net_set_amp_weights takes — a
+    // combined handle's whole vector).  ph: by family — SINGLE_PHASE none (the phase is the MLP of amp.d's n_lin layers below),
+    // AGGREGATE the per-pair phase blocks (raw: the realised outcome's output is the pair's phase; same depth as amp), COMBINED the
+    // "phase head": the last block's W1, b1 and phase rows as a raw block of pair P - 1, packed at ph.w + ph.d.amp_off[P - 1]
+    // (ph.src_off all 0, ph.n_params 0: its parameters live inside the last amplitude block's).
+    // Ownership: d_w is the handle's; a set owns its `w` unless that aliases d_w (the amplitude set at depth 1).
+    naqs::BlockSet amp, ph;
     std::vector<int64_t> phase_src_off;     // per phase linear layer: offset in the flat source
     std::vector<int> phase_K, phase_N;
-    // aggregate_phase: one phase block per pair, described as a second "amplitude-shaped" network (4 raw outputs, no
-    // symmetry, the realised outcome's output is the pair's phase): the amplitude kernels run on it in raw mode
-    // amplitude blocks with more than one hidden layer (naqs_net_create_amp_layers; naqs_amp_deep.hpp): amp_src_off / amp_params
-    // follow their layout, the kernels read the f32 copy d_wdeep (pair n at deep_off[n]) and d_w's amplitude rows are unused
-    int amp_depth = 1;
-    float *d_wdeep = nullptr;
-    int64_t deep_off[naqs::MAXP] = {};
-    int64_t deep_floats = 0;
     char last_deep[96] = {0};               // the deep launches of the last sampler / backward call (naqs_net_last_kernel)
-    // combined amplitude-phase blocks (naqs_net_create_combined): the last block's output layer also carries the phase rows.
-    // dims / d_w / d_wamp hold the amplitude blocks exactly as a plain handle's (the sampler runs unchanged); dph describes the
-    // "phase head" — the last block's W1, b1 and phase rows as a raw block of pair P - 1, packed at d_wph + dph.amp_off[P - 1].
-    // d_cflat = [amplitude blocks in the plain layout (comb_amp floats) | the head (comb_head floats)], re-laid out from the flat
-    // parameters by every re-pack; d_cpart: the backward's per-workgroup partial sums in d_cflat's layout (naqs_grad.hip)
-    bool comb = false, comb_attr_set = false;
+    // COMBINED: d_cflat = [amplitude blocks in the plain layout (comb_amp floats) | the head (comb_head floats)], re-laid out from
+    // the flat parameters by every re-pack; d_cpart: the backward's per-workgroup partial sums in d_cflat's layout (naqs_grad.hip)
+    bool comb_attr_set = false;
     int64_t comb_amp = 0, comb_head = 0;
     float *d_cflat = nullptr, *d_cpart = nullptr;
-    bool aggregate = false;
-    naqs::NetDims dph{};
-    int64_t ph_src_off[naqs::MAXP] = {};          // per pair: offset of its phase block in the flat source
-    int64_t ph_params = 0;
-    float *d_wph = nullptr;                 // packed phase blocks (layout of the amplitude rows; deep phase blocks: naqs_amp_deep.hpp's)
-    // aggregate_phase with 2..4 hidden layers in every block (naqs_net_create_agg_layers): the amplitude set is exactly a
-    // naqs_net_create_amp_layers handle's (amp_depth, d_wdeep, deep_off); the phase blocks have the same depth and are packed
-    // into d_wph in the deep layout, pair n at ph_deep_off[n] (dph describes them: sym 0, 4 or 3 raw outputs)
-    int64_t ph_deep_off[naqs::MAXP] = {};
-    int64_t ph_deep_floats = 0;
-    float *d_w = nullptr;                   // [amp params | packed phase layers]
+    float *d_w = nullptr;                   // [amplitude rows (unused by deep blocks) | packed phase layers]; null: deep AGGREGATE
     unsigned short *d_wh = nullptr;         // phase layers as 3 bf16 planes (phase_kernel_bf16x3)
     int64_t wh_elems = 0;
     unsigned short *d_wamp = nullptr;       // amplitude blocks as bf16x3 MFMA fragments (phase kernel prologue); null: amp_kernel
@@ -405,8 +421,8 @@ int net_backward_pack_jobs(naqs_net *net, WbPackJobs *jobs);
 // naqs_logpsi.hip: the amplitude blocks' share of a training step's re-pack, if it is still waiting for a launch to host it
 // (naqs_pack.hpp) — for every reader of the amplitude rows / fragments that is not that launch
 int net_flush_amp_pack(naqs_net *net, hipStream_t s);
-// naqs_grad.hip: d/d theta sum_i g_i f(key_i) for one set of per-pair blocks (amplitude blocks, or the phase blocks of an
-// aggregate-phase network with raw = 1); grad_dev receives n_block_params floats in state_dict order
+// naqs_grad.hip: d/d theta sum_i g_i f(key_i) for one set of per-pair blocks (f = log|psi| for the amplitude set, the phase for a
+// raw set); grad_dev receives set.n_params floats in state_dict order
 // With `defer` the fixed-order reduction of the workgroups' partial sums is not launched but described there, for the
 // caller's one launch that finishes the whole gradient (naqs_phase_grad.hip: grad_finish_kernel); `slot` picks the half of
 // the partial-sum scratch (two block sets may be pending at once).
@@ -415,12 +431,10 @@ struct BlockReduceJob {
     int n_partials = 0;
     const float *partial = nullptr;
 };
-int net_blocks_backward(naqs_net *net, const NetDims &d, const float *w, const int64_t *src_off, int64_t n_block_params,
-                        int64_t M, const uint64_t *keys_dev, const float *g_dev, float *grad_dev, int raw, hipStream_t s,
-                        BlockReduceJob *defer = nullptr, int slot = 0);
+int net_blocks_backward(naqs_net *net, const BlockSet &set, int64_t M, const uint64_t *keys_dev, const float *g_dev, float *grad_dev,
+                        hipStream_t s, BlockReduceJob *defer = nullptr, int slot = 0);
 namespace ampbw { struct AmpSrc; }
-int net_blocks_backward_plan(naqs_net *net, const NetDims &d, const int64_t *src_off, int64_t n_block_params, int64_t M, int slot,
-                             BlockReduceJob *job, ampbw::AmpSrc *src);
+int net_blocks_backward_plan(naqs_net *net, const BlockSet &set, int64_t M, int slot, BlockReduceJob *job, ampbw::AmpSrc *src);
 int net_blocks_backward2(naqs_net *net, int64_t M, const uint64_t *keys_dev, const float *g_amp, const float *g_ph, int g_stride,
                          BlockReduceJob jobs[2], hipStream_t s);
 // Adam (Kingma & Ba) on element i of a flat parameter vector, torch.optim.Adam's update rule (no amsgrad):
@@ -439,11 +453,17 @@ inline AdamArgs adam_args(float *p, float *m, float *v, double lr, double beta1,
     return a;
 }
 inline CombLayout comb_layout(const naqs_net *net) {
-    const NetDims &d = net->dims;
+    const NetDims &d = net->amp.d;
     CombLayout c;
-    c.last = net->amp_src_off[d.P - 1]; c.amp = net->comb_amp; c.total = net->n_params;
-    c.Ha = d.Ha; c.nin = 2 * (d.P - 1); c.na = d.n_out_amp; c.nph = net->dph.n_out_amp;
+    c.last = net->amp.src_off[d.P - 1]; c.amp = net->comb_amp; c.total = net->n_params;
+    c.Ha = d.Ha; c.nin = 2 * (d.P - 1); c.na = d.n_out_amp; c.nph = net->ph.d.n_out_amp;
     return c;
+}
+// what the call sites ask of the family
+inline bool has_phase_mlp(const naqs_net *net) { return net->family == Family::SINGLE_PHASE; }      // ... whose backward reads saved activations
+inline bool has_second_set(const naqs_net *net) { return net->family != Family::SINGLE_PHASE; }     // net->ph is in use, and in the scratch
+inline bool shard_calls_supported(const naqs_net *net) {                                            // naqs_vmc_shard_*: else the replicated step only
+    return net->family == Family::SINGLE_PHASE || (net->family == Family::AGGREGATE && !net->amp.deep());
 }
 // naqs_grad.hip: the combined handle's backward — amplitude blocks on g[:, 0] (g_stride 2) or g (g_stride 1), with_head: the phase
 // head on g[:, 1] — reduced in fixed order into grad_dev in the flat layout (the head's W1 / b1 added to the last block's), and

@@ -241,7 +241,7 @@ __device__ __forceinline__ void pack_amp_body(const float *__restrict__ flat, co
     const int Ha = d.Ha, nout = d.n_out_amp, nin = n == 0 ? 1 : 2 * n;
     const float *src = flat + so.off[n];
     float *dst = w + d.amp_off[n];
-    const int S = (nin + 1 + 5 + 3) & ~3, total = Ha * S + 8;
+    const int S = amp_row_stride(nin), total = amp_block_floats(Ha, nin);
     for (int e = bx * 256 + threadIdx.x; e < total; e += nbx * 256) {
         float v = 0.0f;
         if (e < Ha * S) {

@@ -644,7 +644,7 @@ struct TrainLayout {            // carve-up of net->d_train for `cap` rows
 inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 TrainLayout train_layout(const naqs_net *net, int64_t cap) {
-    const NetDims &d = net->dims;
+    const NetDims &d = net->amp.d;
     TrainLayout L{};
     size_t off = 0;
     const int H = d.n_lin - 1;
@@ -703,7 +703,7 @@ size_t wb_offset(const naqs_net *net, int l) {
 // phase weights, row-major and zero-padded to multiples of 64 in both dimensions (Wb_l [Np][Kp]): what the packing
 // launch of naqs_net_set_weights has to copy (layer 0 has no delta to propagate)
 int naqs::net_backward_pack_jobs(naqs_net *net, naqs::WbPackJobs *jobs) {
-    const NetDims &d = net->dims;
+    const NetDims &d = net->amp.d;
     if (!net->d_wb) {
         HIP_TRY(hipMalloc((void **)&net->d_wb, wb_offset(net, d.n_lin) * sizeof(float)));
     }
@@ -725,7 +725,7 @@ NAQS_API int naqs_net_train_forward(naqs_net_t *net, int64_t M, const uint64_t *
     DeviceGuard guard;
     int st = guard.init(net->device);
     if (st != NAQS_OK) return st;
-    if (net->aggregate || net->comb) {                      // the per-pair blocks are recomputed by the backward pass: nothing to keep
+    if (!naqs::has_phase_mlp(net)) {                        // the per-pair blocks are recomputed by the backward pass: nothing to keep
         naqs::ElocFeed none{};
         return naqs::net_logpsi_impl(net, M, keys_dev, logpsi_dev, stream, none, naqs::PhaseSave{});
     }
@@ -736,7 +736,7 @@ NAQS_API int naqs_net_train_forward(naqs_net_t *net, int64_t M, const uint64_t *
     naqs::PhaseSave save;
     save.x = reinterpret_cast<float *>(base + L.x);
     save.x_ld = L.x_ld;
-    for (int l = 0; l + 1 < net->dims.n_lin; ++l) {
+    for (int l = 0; l + 1 < net->amp.d.n_lin; ++l) {
         save.act[l] = reinterpret_cast<float *>(base + L.act[l]);
         save.act_ld[l] = L.act_ld[l];
     }
@@ -760,14 +760,14 @@ NAQS_API int naqs_net_train_forward_eloc(naqs_net_t *net, naqs_ham_t *ham, int64
         return NAQS_OK;
     }
     naqs::PhaseSave save;
-    if (!net->aggregate && !net->comb) {
+    if (naqs::has_phase_mlp(net)) {
         st = ensure_train_scratch(net, M);
         if (st != NAQS_OK) return st;
         const TrainLayout L = train_layout(net, net->train_cap);
         char *base = static_cast<char *>(net->d_train);
         save.x = reinterpret_cast<float *>(base + L.x);
         save.x_ld = L.x_ld;
-        for (int l = 0; l + 1 < net->dims.n_lin; ++l) {
+        for (int l = 0; l + 1 < net->amp.d.n_lin; ++l) {
             save.act[l] = reinterpret_cast<float *>(base + L.act[l]);
             save.act_ld[l] = L.act_ld[l];
         }
@@ -900,7 +900,7 @@ static int train_backward_impl(naqs_net_t *net, int64_t M, const uint64_t *keys_
         if (stj != NAQS_OK) return stj;
     }
     if (!net->have_weights || !net->have_wb) return NAQS_ERR_INVALID;
-    if (!net->aggregate && !net->comb && (M > net->train_cap || !net->d_train)) return NAQS_ERR_INVALID;   // naqs_net_train_forward of the same batch comes first
+    if (naqs::has_phase_mlp(net) && (M > net->train_cap || !net->d_train)) return NAQS_ERR_INVALID;   // naqs_net_train_forward of the same batch comes first
     DeviceGuard guard;
     int st = guard.init(net->device);
     if (st != NAQS_OK) return st;
@@ -912,14 +912,14 @@ static int train_backward_impl(naqs_net_t *net, int64_t M, const uint64_t *keys_
     }
     // combined amplitude-phase blocks: the amplitude blocks on g[:, 0] and the phase head on g[:, 1] in one launch, then the
     // fixed-order reduction into the flat layout (+ Adam) in another (naqs_grad.hip)
-    if (net->comb) return naqs::net_comb_backward(net, M, keys_dev, g_dev, 2, true, grad_dev, adam, s);
+    if (net->family == naqs::Family::COMBINED) return naqs::net_comb_backward(net, M, keys_dev, g_dev, 2, true, grad_dev, adam, s);
     GradFinish F;
-    if (net->aggregate) {
+    if (net->family == naqs::Family::AGGREGATE) {
         // both sets of per-pair blocks through the same backward kernel: amplitude blocks on g[:, 0], phase blocks (raw
         // outputs, no conditional) on g[:, 1]; the forward scratch ([2 P][cap] floats, free by now) holds the two columns.
         // (deep blocks, naqs_net_create_agg_layers: the same two forms on the deep kernels — naqs_grad.hip)
         if (M > net->cap_M || !net->d_scratch) return NAQS_ERR_INVALID;
-        if (net->dims.Ha == net->dph.Ha && net->dims.P == net->dph.P && (naqs::env_int("NAQS_AGG_MERGE", 7) & 2)) {
+        if (net->amp.d.Ha == net->ph.d.Ha && net->amp.d.P == net->ph.d.P && (naqs::env_int("NAQS_AGG_MERGE", 7) & 2)) {
             // one launch for both sets, the two columns of g read where they are
             st = naqs::net_blocks_backward2(net, M, keys_dev, g_dev, g_dev + 1, 2, F.set, s);
             if (st != NAQS_OK) return st;
@@ -928,20 +928,18 @@ static int train_backward_impl(naqs_net_t *net, int64_t M, const uint64_t *keys_
             NAQS_KLAUNCH(split_g2_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, M, reinterpret_cast<const float2 *>(g_dev),
                                g_amp, g_ph);
             HIP_TRY(hipGetLastError());
-            st = naqs::net_blocks_backward(net, net->dims, net->d_w, net->amp_src_off, net->amp_params, M, keys_dev, g_amp, grad_dev, 0, s,
-                                           &F.set[0], 0);
+            st = naqs::net_blocks_backward(net, net->amp, M, keys_dev, g_amp, grad_dev, s, &F.set[0], 0);
             if (st != NAQS_OK) return st;
-            st = naqs::net_blocks_backward(net, net->dph, net->d_wph, net->ph_src_off, net->ph_params, M, keys_dev, g_ph,
-                                           grad_dev + net->amp_params, 1, s, &F.set[1], 1);
+            st = naqs::net_blocks_backward(net, net->ph, M, keys_dev, g_ph, grad_dev + net->amp.n_params, s, &F.set[1], 1);
             if (st != NAQS_OK) return st;
         }
         F.n_sets = 2;
-        F.set_end[0] = net->amp_params; F.set_end[1] = net->amp_params + net->ph_params;
-        F.set_out[0] = 0; F.set_out[1] = net->amp_params;
+        F.set_end[0] = net->amp.n_params; F.set_end[1] = net->amp.n_params + net->ph.n_params;
+        F.set_out[0] = 0; F.set_out[1] = net->amp.n_params;
         F.total = F.set_end[1];
         return launch_grad_finish(F, GradWJobs{}, nullptr, nullptr, grad_dev, adam, s);
     }
-    const NetDims &d = net->dims;
+    const NetDims &d = net->amp.d;
     const TrainLayout L = train_layout(net, net->train_cap);
     char *base = static_cast<char *>(net->d_train);
     float *x = reinterpret_cast<float *>(base + L.x);
@@ -983,14 +981,13 @@ static int train_backward_impl(naqs_net_t *net, int64_t M, const uint64_t *keys_
         HIP_TRY(hipGetLastError());
     }
     // NAQS_TRAIN_MEGA=0: every piece its own launch
-    const bool mega = H == 2 && d.Ha == 64 && net->amp_depth == 1 && naqs::env_int("NAQS_TRAIN_MEGA", 1) == 1;
+    const bool mega = H == 2 && d.Ha == 64 && !net->amp.deep() && naqs::env_int("NAQS_TRAIN_MEGA", 1) == 1;
     naqs::ampbw::AmpSrc amp_src{};
-    if (mega) st = naqs::net_blocks_backward_plan(net, net->dims, net->amp_src_off, net->amp_params, M, 0, &F.set[0], &amp_src);
-    else st = naqs::net_blocks_backward(net, net->dims, net->d_w, net->amp_src_off, net->amp_params, M, keys_dev, g_amp, grad_dev, 0, s,
-                                        &F.set[0], 0);
+    if (mega) st = naqs::net_blocks_backward_plan(net, net->amp, M, 0, &F.set[0], &amp_src);
+    else st = naqs::net_blocks_backward(net, net->amp, M, keys_dev, g_amp, grad_dev, s, &F.set[0], 0);
     if (st != NAQS_OK) return st;
     F.n_sets = 1;
-    F.set_end[0] = net->amp_params;
+    F.set_end[0] = net->amp.n_params;
 
     // phase block.  First the chain of deltas, output layer down (the critical path: each needs the one above) ...
     if (seeds == nullptr) {
@@ -1062,7 +1059,7 @@ static int train_backward_impl(naqs_net_t *net, int64_t M, const uint64_t *keys_
     if (mega) {
         A.M = M; A.cpart = cpart; A.bpart = bpart; A.gw_bid0 = J.block_end[0];
         A.amp_wgs = F.set[0].n_partials; A.n_amp = A.amp_wgs * d.P;
-        A.amp_w = net->d_w; A.g_amp = g_amp; A.keys = keys_dev;
+        A.amp_w = net->amp.w; A.g_amp = g_amp; A.keys = keys_dev;
         A.amp_partial = const_cast<float *>(F.set[0].partial); A.amp_stride = F.set[0].stride;
         const size_t lds = std::max(naqs::ampbw::smem_floats(d), (size_t)std::max(TB * LDD + CH * LDT, 2 * CH * LDT)) * sizeof(float);
         if (lds > 64 * 1024) return NAQS_ERR_UNSUPPORTED;
@@ -1089,12 +1086,12 @@ static int train_backward_impl(naqs_net_t *net, int64_t M, const uint64_t *keys_
     if (adam != nullptr && naqs::env_int("NAQS_PACK_OVERLAP", 2) >= 2 && net->d_wamp != nullptr && net->packed_fmt == 2 && d.P > HEAD_MAX_PAIRS &&
         naqs::amp_raw_floats(d.Ha, d.n_out_amp, HEAD_MAX_PAIRS - 1) <= HEAD_EPT * 256 && F.set_out[0] == 0) {
         hp.pairs = HEAD_MAX_PAIRS; hp.Ha = d.Ha; hp.nout = d.n_out_amp; hp.wamp = net->d_wamp;
-        bool contiguous = net->amp_src_off[0] == 0;
+        bool contiguous = net->amp.src_off[0] == 0;
         for (int p = 0; p < HEAD_MAX_PAIRS; ++p) {
-            hp.off[p] = net->amp_src_off[p] - net->amp_src_off[0];
-            contiguous = contiguous && net->amp_src_off[p + 1] - net->amp_src_off[p] == naqs::amp_raw_floats(d.Ha, d.n_out_amp, p);
+            hp.off[p] = net->amp.src_off[p] - net->amp.src_off[0];
+            contiguous = contiguous && net->amp.src_off[p + 1] - net->amp.src_off[p] == naqs::amp_raw_floats(d.Ha, d.n_out_amp, p);
         }
-        hp.skip = net->amp_src_off[HEAD_MAX_PAIRS] - net->amp_src_off[0];
+        hp.skip = net->amp.src_off[HEAD_MAX_PAIRS] - net->amp.src_off[0];
         if (!contiguous) hp = HeadPairs{};
     }
     st = launch_grad_finish(F, J, cpart, bpart, grad_dev, adam, s, 0, -1, hp.pairs > 0 ? &hp : nullptr);
@@ -1133,7 +1130,7 @@ NAQS_API int naqs_vmc_step(naqs_net_t *net, naqs_ham_t *ham, int64_t n_samples, 
         bool launched = false; int64_t rows = 0; naqs::ElocFeed feed{}; naqs::PhaseForm form;
         int operator()() override {
             const int64_t hint = net->spec_hint;
-            if (hint <= 0 || net->aggregate || net->comb || !ham || !logpsi || naqs::env_int("NAQS_SPEC_FORWARD", 1) == 0) return NAQS_OK;
+            if (hint <= 0 || !naqs::has_phase_mlp(net) || !ham || !logpsi || naqs::env_int("NAQS_SPEC_FORWARD", 1) == 0) return NAQS_OK;
             if (naqs::ham_device(ham) != net->device) return NAQS_OK;
             int64_t cover = std::min<int64_t>(max_unique, hint + std::max<int64_t>(64, hint / 8));
             if (naqs::env_int("NAQS_DEBUG_SPEC_SHRINK", 0) != 0) cover = std::max<int64_t>(16, hint / 2);      // (tests: a launch that does not fit)
@@ -1146,7 +1143,7 @@ NAQS_API int naqs_vmc_step(naqs_net_t *net, naqs_ham_t *ham, int64_t n_samples, 
             naqs::PhaseSave save;
             save.x = reinterpret_cast<float *>(base + L.x);
             save.x_ld = L.x_ld;
-            for (int l = 0; l + 1 < net->dims.n_lin; ++l) {
+            for (int l = 0; l + 1 < net->amp.d.n_lin; ++l) {
                 save.act[l] = reinterpret_cast<float *>(base + L.act[l]);
                 save.act_ld[l] = L.act_ld[l];
             }
@@ -1174,7 +1171,7 @@ NAQS_API int naqs_vmc_step(naqs_net_t *net, naqs_ham_t *ham, int64_t n_samples, 
     if (spec_hit) ++net->spec_hits;
     // small tables: the weighted sums of E_loc are formed by the first workgroup of the backward pass's seed kernel (same
     // arithmetic, same order: naqs_reduce.hpp) instead of by a launch between E_loc and the seeds (NAQS_FUSE_SUMS=0: the launch)
-    const bool form_sums = !net->aggregate && net->dims.n_lin >= 2 && M <= SUMS_FUSE_MAX_ROWS && sums_dev != nullptr &&
+    const bool form_sums = naqs::has_phase_mlp(net) && net->amp.d.n_lin >= 2 && M <= SUMS_FUSE_MAX_ROWS && sums_dev != nullptr &&
                            net->d_sum_words != nullptr && naqs::env_int("NAQS_FUSE_SUMS", 1) != 0;
     if (spec_hit) {
         if (!eloc_dev || (!form_sums && (!weights_dev || !sums_dev))) return NAQS_ERR_INVALID;
@@ -1289,7 +1286,7 @@ NAQS_API int naqs_vmc_shard_sample_forward(naqs_net_t *net, int64_t n_samples, u
                                            void *stream) {
     if (!net || !info_host || !logpsi_shard_dev || world < 1 || rank < 0 || rank >= world) return NAQS_ERR_INVALID;
     info_host[2] = 0;
-    if (net->comb || (net->aggregate && net->amp_depth > 1)) return NAQS_ERR_UNSUPPORTED;     // (combined blocks, deep aggregate-phase
+    if (!naqs::shard_calls_supported(net)) return NAQS_ERR_UNSUPPORTED;                      // (combined blocks, deep aggregate-phase
                                                                                              //  blocks: the replicated step only)
     int64_t info2[2] = {0, 0};
     DeviceGuard guard;
@@ -1315,7 +1312,7 @@ NAQS_API int naqs_vmc_shard_update(naqs_net_t *net, const float *grad_dev, float
                                    double lr, double beta1, double beta2, double eps, double weight_decay, int64_t adam_step,
                                    void *stream) {
     if (!net || !grad_dev || !param_dev || !exp_avg_dev || !exp_avg_sq_dev || adam_step < 1) return NAQS_ERR_INVALID;
-    if (net->comb || (net->aggregate && net->amp_depth > 1)) return NAQS_ERR_UNSUPPORTED;     // (combined blocks, deep aggregate-phase
+    if (!naqs::shard_calls_supported(net)) return NAQS_ERR_UNSUPPORTED;                      // (combined blocks, deep aggregate-phase
                                                                                              //  blocks: the replicated step only)
     DeviceGuard guard;
     int st = guard.init(net->device);
@@ -1335,12 +1332,12 @@ static int train_backward_vmc_impl(naqs_net_t *net, int64_t M, const uint64_t *k
                                    const double *w_dev, const double *sums_dev, float *g_dev, double *ev_dev, float *grad_dev,
                                    void *stream, const naqs::AdamArgs *adam, bool form_sums) {
     if (!net || !sums_dev || !ev_dev || !g_dev || (M > 0 && (!eloc_dev || !w_dev))) return NAQS_ERR_INVALID;
-    if (net->aggregate || net->comb || M == 0) {      // per-pair phase blocks, combined blocks (or nothing to do): the two separate calls
+    if (!naqs::has_phase_mlp(net) || M == 0) {      // per-pair phase blocks, combined blocks (or nothing to do): the two separate calls
         int st = naqs_vmc_loss_grad_ev(M, eloc_dev, w_dev, sums_dev, g_dev, ev_dev, stream);
         if (st != NAQS_OK) return st;
         return train_backward_impl(net, M, keys_dev, g_dev, grad_dev, stream, nullptr, adam);
     }
-    if (form_sums && net->dims.n_lin < 2) return NAQS_ERR_INVALID;              // (the caller's condition: the seed + delta kernel runs)
+    if (form_sums && net->amp.d.n_lin < 2) return NAQS_ERR_INVALID;              // (the caller's condition: the seed + delta kernel runs)
     const VmcSeeds seeds{eloc_dev, w_dev, sums_dev, g_dev, ev_dev, form_sums};
     return train_backward_impl(net, M, keys_dev, g_dev, grad_dev, stream, &seeds, adam);
 }

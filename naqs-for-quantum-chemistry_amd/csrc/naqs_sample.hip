@@ -243,7 +243,7 @@ __device__ __forceinline__ void expand_probs(const NetDims &d, const float *__re
                                              const naqs::ushort_t *__restrict__ wamp = nullptr) {
     const int q = threadIdx.x & 3;
     const int nin = n == 0 ? 1 : 2 * n;
-    const int S = (nin + 1 + 5 + 3) & ~3;
+    const int S = naqs::amp_row_stride(nin);
     const uint32_t abits = ab & 0xffffu, bbits = ab >> 16;
     const bool swap = d.sym && abits > bbits;                                  // nade.py:519-530
     const uint32_t first = swap ? bbits : abits, second = swap ? abits : bbits;
@@ -335,7 +335,7 @@ __device__ __forceinline__ void split_quad(const int n, const uint32_t ab, const
 __device__ __forceinline__ void stage_pair_weights(const NetDims &d, const float *__restrict__ w, const int n, float *s_w,
                                                    const int nthreads) {
     const int nin = n == 0 ? 1 : 2 * n;
-    const int total = d.Ha * ((nin + 1 + 5 + 3) & ~3) + 8;
+    const int total = naqs::amp_block_floats(d.Ha, nin);
     const f32x4 *src = reinterpret_cast<const f32x4 *>(w + d.amp_off[n]);
     f32x4 *dst = reinterpret_cast<f32x4 *>(s_w);
     for (int e = threadIdx.x; e < total / 4; e += nthreads) dst[e] = src[e];
@@ -972,7 +972,7 @@ static int net_sample_enqueue(naqs_net_t *net, int64_t n_samples, uint64_t seed,
     if (st != NAQS_OK) return st;
     st = naqs::poll_check(net->poll);              // an earlier launch's device-side wait that gave up (naqs_poll.hpp)
     if (st != NAQS_OK) return st;
-    const NetDims &d = net->dims;
+    const NetDims &d = net->amp.d;
     const int64_t cap = max_unique;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     st = naqs::net_info_alloc(net);
@@ -1033,7 +1033,7 @@ static int net_sample_enqueue(naqs_net_t *net, int64_t n_samples, uint64_t seed,
     // (94 us against 38 + 18 for the fifth level on its own: sixteen latency-bound waves on one CU)
     const int head = naqs::env_int("NAQS_SAMPLE_HEAD", 1);
     // deep amplitude blocks (naqs_net_create_amp_layers): one expand + scatter pair per level (sample_expand_deep_kernel)
-    const bool deep = net->amp_depth > 1;
+    const bool deep = net->amp.deep();
     const bool use_head = !deep && head >= 1 && ((head >= 2 && d.P > 5 && cap >= 1024) || (d.P > 4 && cap >= 256));
     if (!(use_head && !(head >= 2 && d.P > 5 && cap >= 1024))) {
         // no launch of this call can host a pending amplitude re-pack (naqs_vmc_step leaves it to the four-level head launch
@@ -1045,11 +1045,11 @@ static int net_sample_enqueue(naqs_net_t *net, int64_t n_samples, uint64_t seed,
         const bool big = head >= 2 && d.P > 5 && cap >= 1024;
         const int hl = big ? 5 : 4;
         const int nin = 2 * (hl - 1);
-        const size_t lds = wamp ? (size_t)(big ? 16 : 4) * mf_wave_bytes : ((size_t)d.Ha * ((nin + 1 + 5 + 3) & ~3) + 8) * sizeof(float);
+        const size_t lds = wamp ? (size_t)(big ? 16 : 4) * mf_wave_bytes : (size_t)naqs::amp_block_floats(d.Ha, nin) * sizeof(float);
         if (big) {
             if (lds > 64 * 1024)
                 (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&sample_head_kernel<1024, 5>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            NAQS_KLAUNCH((sample_head_kernel<1024, 5>), dim3(1), dim3(1024), lds, s, d, net->d_w, b, n_samples, k0, k1, wamp, naqs::PackPhaseArgs{});
+            NAQS_KLAUNCH((sample_head_kernel<1024, 5>), dim3(1), dim3(1024), lds, s, d, net->amp.w, b, n_samples, k0, k1, wamp, naqs::PackPhaseArgs{});
         } else {
             // the last update's re-pack, if a training step left it pending, rides in this launch: the phase layers' share and
             // (matrix-core form of the block MLPs, and the fragments of the hl pairs workgroup 0 reads packed by the update's own
@@ -1057,7 +1057,7 @@ static int net_sample_enqueue(naqs_net_t *net, int64_t n_samples, uint64_t seed,
             naqs::PackPhaseArgs pk;
             st = naqs::net_take_pending_pack(net, s, &pk, wamp != nullptr ? hl : 0);
             if (st != NAQS_OK) return st;
-            NAQS_KLAUNCH((sample_head_kernel<256, 4>), dim3(1 + (unsigned)pk.n_wgs), dim3(256), lds, s, d, net->d_w, b, n_samples, k0, k1, wamp, pk);
+            NAQS_KLAUNCH((sample_head_kernel<256, 4>), dim3(1 + (unsigned)pk.n_wgs), dim3(256), lds, s, d, net->amp.w, b, n_samples, k0, k1, wamp, pk);
         }
         HIP_TRY(hipGetLastError());
         n_first = hl;
@@ -1108,20 +1108,20 @@ static int net_sample_enqueue(naqs_net_t *net, int64_t n_samples, uint64_t seed,
         }
         const int n_end = n + nl - 1;                         // last level of this launch
         const int nin = n_end == 0 ? 1 : 2 * n_end;
-        const size_t lds = wamp ? (size_t)(SB / WAVE) * mf_wave_bytes : ((size_t)d.Ha * ((nin + 1 + 5 + 3) & ~3) + 8) * sizeof(float);
+        const size_t lds = wamp ? (size_t)(SB / WAVE) * mf_wave_bytes : (size_t)naqs::amp_block_floats(d.Ha, nin) * sizeof(float);
         const int last = n_end == d.P - 1 ? 1 : 0;
         if (nl > 1) {
             const int E = 64 >> (2 * (nl - 1));
             const unsigned grid_m = (unsigned)((std::min(bound, cap) + E - 1) / E);
             const uint32_t tag = (net->samp_seq << 8) | (uint32_t)(n + 1);
             if (nl == 4)
-                NAQS_KLAUNCH((sample_multi_kernel<4>), dim3(grid_m), dim3(SB), lds, s, d, net->d_w, n, b, half, k0, k1, tag, cap, last,
+                NAQS_KLAUNCH((sample_multi_kernel<4>), dim3(grid_m), dim3(SB), lds, s, d, net->amp.w, n, b, half, k0, k1, tag, cap, last,
                                    keys_dev, counts_dev, probs_dev, wamp, early, seq);
             else if (nl == 3)
-                NAQS_KLAUNCH((sample_multi_kernel<3>), dim3(grid_m), dim3(SB), lds, s, d, net->d_w, n, b, half, k0, k1, tag, cap, last,
+                NAQS_KLAUNCH((sample_multi_kernel<3>), dim3(grid_m), dim3(SB), lds, s, d, net->amp.w, n, b, half, k0, k1, tag, cap, last,
                                    keys_dev, counts_dev, probs_dev, wamp, early, seq);
             else
-                NAQS_KLAUNCH((sample_multi_kernel<2>), dim3(grid_m), dim3(SB), lds, s, d, net->d_w, n, b, half, k0, k1, tag, cap, last,
+                NAQS_KLAUNCH((sample_multi_kernel<2>), dim3(grid_m), dim3(SB), lds, s, d, net->amp.w, n, b, half, k0, k1, tag, cap, last,
                                    keys_dev, counts_dev, probs_dev, wamp, early, seq);
             HIP_TRY(hipGetLastError());
             for (int i = 0; i < nl; ++i) bound = bound > cap ? bound : bound * 4;
@@ -1133,20 +1133,19 @@ static int net_sample_enqueue(naqs_net_t *net, int64_t n_samples, uint64_t seed,
         const unsigned grid_e = (unsigned)((std::min(bound, cap) + EXP_PARENTS - 1) / EXP_PARENTS);
         if (fused_levels && (int64_t)grid_e <= resident_wg) {
             const uint32_t tag = (net->samp_seq << 8) | (uint32_t)(n + 1);
-            NAQS_KLAUNCH(sample_level_kernel, dim3(grid_e), dim3(SB), lds, s, d, net->d_w, n, b, half, k0, k1, tag, cap, last,
+            NAQS_KLAUNCH(sample_level_kernel, dim3(grid_e), dim3(SB), lds, s, d, net->amp.w, n, b, half, k0, k1, tag, cap, last,
                                keys_dev, counts_dev, probs_dev, clk_dev, wamp, early, seq);
             HIP_TRY(hipGetLastError());
         } else {
             if (deep) {
-                const naqs::DeepAmp da = naqs::deep_amp(net);
-                switch (d.Ha >> 4) {
-#define NAQS_DEEP(C) case C: NAQS_KLAUNCH(sample_expand_deep_kernel<C>, dim3(grid_e), dim3(SB), 0, s, d, net->d_wdeep, da, n, b, half, k0, k1); break;
-                    NAQS_DEEP(1) NAQS_DEEP(2) NAQS_DEEP(3) NAQS_DEEP(4) NAQS_DEEP(5) NAQS_DEEP(6) NAQS_DEEP(7) NAQS_DEEP(8)
-#undef NAQS_DEEP
-                    default: return NAQS_ERR_UNSUPPORTED;
-                }
+                const naqs::DeepAmp da = naqs::deep_blocks(net->amp);
+                st = naqs::dispatch_width(d.Ha >> 4, [&](auto c) -> int {
+                    NAQS_KLAUNCH(sample_expand_deep_kernel<decltype(c)::value>, dim3(grid_e), dim3(SB), 0, s, d, net->amp.w, da, n, b, half, k0, k1);
+                    return NAQS_OK;
+                });
+                if (st != NAQS_OK) return st;
             } else {
-                NAQS_KLAUNCH(sample_expand_kernel, dim3(grid_e), dim3(SB), lds, s, d, net->d_w, n, b, half, k0, k1, wamp);
+                NAQS_KLAUNCH(sample_expand_kernel, dim3(grid_e), dim3(SB), lds, s, d, net->amp.w, n, b, half, k0, k1, wamp);
             }
             HIP_TRY(hipGetLastError());
             NAQS_KLAUNCH(sample_scatter_kernel, dim3(grid), dim3(SB), 0, s, d, n, b, half, cap, last, keys_dev, counts_dev,

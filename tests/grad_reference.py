@@ -220,10 +220,11 @@ def sector(name):
 
 
 def sector_net(name, device="cuda", seed=0, masking="PARTIAL", aggregate=False, phase_sym=False, amp_layers=1, amp_hidden=64,
-               phase_hidden=(512, 512)):
+               phase_hidden=(512, 512), combined=False):
     """(hilbert, network) on sector ``name``: default-initialised from ``seed``; by default the published shape (amplitude
     width 64, one phase MLP [512, 512], amplitude spin symmetry, PARTIAL masking).  ``aggregate``: one phase block of
-    ``phase_hidden`` per pair (run.py's default ansatz); ``amp_layers``: hidden layers per amplitude block."""
+    ``phase_hidden`` per pair (run.py's default ansatz); ``amp_layers``: hidden layers per amplitude block; ``combined``: -comb_amp_phase (the
+    last block's output layer carries the phase rows)."""
     from naqs_amd.hilbert import Encoding, Hilbert
     from naqs_amd.nade import NadeMasking
     from naqs_amd.wavefunction import NAQSComplex_NADE_orbitals
@@ -233,7 +234,7 @@ def sector_net(name, device="cuda", seed=0, masking="PARTIAL", aggregate=False, 
     wf = NAQSComplex_NADE_orbitals(hil, device=device, qubit_ordering=-1, masking=NadeMasking[masking],
                                    amp_hidden_size=[amp_hidden] * amp_layers, phase_hidden_size=list(phase_hidden),
                                    use_amp_spin_sym=True, use_phase_spin_sym=phase_sym, aggregate_phase=aggregate,
-                                   n_alpha_electrons=na, n_beta_electrons=nb)
+                                   combined_amp_phase_blocks=combined, n_alpha_electrons=na, n_beta_electrons=nb)
     return hil, wf
 
 

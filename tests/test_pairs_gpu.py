@@ -15,6 +15,8 @@ NONE masking, two amplitude layers) at P = 2, 4, 5, 13 and 16.
 * sampler: probs against exp(2 log|psi|_f64); an exact chi-square over the whole space (P <= 14); a level-by-level
   multinomial test of every tree node (P = 7, 15, 16, FULL masking); each with a host-side power check; every launch cut
   draws the same bits;
+* every kind of handle (single phase, deep single phase, aggregate, deep aggregate, combined) with 16-unit blocks of 5 and 3
+  outputs at P = 2 and 3, where every per-pair offset of the packed copies is rounded: forward, backward, sampler probs;
 * the library's training loop at P <= 5;
 * E_loc of every Hamiltonian the reference ships against the oracle, the chunk length each handle derives, and 32-bit keys.
 
@@ -228,9 +230,12 @@ def test_forward_against_float64(name, variant):
 # --------------------------------------------------------------------------------------------------------- backward
 @pytest.mark.parametrize("name", NAMES)
 def test_backward_against_float64(name):
+    _check_backward(name, *_net(name))
+
+
+def _check_backward(name, hil, wf):
     from test_backward_gpu import BOUND, TAU, W0_FUSE, _dev, _grads, _rel_err, _sums, _zero_grad, _c2
     _threads()
-    hil, wf = _net(name)
     fused = wf.fused()
     assert fused is not None and fused.train_mode == "hip"
     sizes = sorted({1, min(hil.size, 17), min(hil.size, 3000)} | ({W0_FUSE + 1} if hil.size > W0_FUSE else set()))
@@ -243,7 +248,7 @@ def test_backward_against_float64(name):
         ks = np.sort(keys[:m])
         st = _states(hil, ks)
         lp, margin = gr.log_psi_and_kink_margin(wf64, st)
-        e = rs.normal(-1.0 * _P(name), 0.5, m) + 1j * rs.normal(0.0, 1e-3, m)
+        e = rs.normal(-1.0 * (hil.N // 2), 0.5, m) + 1j * rs.normal(0.0, 1e-3, m)
         w = rs.uniform(0.5, 1.5, m)
         near = margin < TAU
         w[near] = 0.0
@@ -288,9 +293,12 @@ def test_backward_against_float64(name):
 @pytest.mark.parametrize("name", NAMES)
 def test_sampler_probs_and_structure(name):
     """probs within 2 (log|psi| bound) + 8 P 2^-24 of exp(2 log|psi|_f64); keys ascending, unique, physical; sum counts <= n."""
+    _check_sampler_probs(name, *_net(name))
+
+
+def _check_sampler_probs(name, hil, wf):
     import test_forward_f64_gpu as tf
     _threads()
-    hil, wf = _net(name)
     fused = wf.fused()
     n = 10 ** 6
     keys, counts, probs = fused.sample(n, seed=20261016, max_unique=1 << 21)
@@ -305,6 +313,57 @@ def test_sampler_probs_and_structure(name):
     print(f"[sampler probs {name} P={P}] {len(k)} unique, {c.sum()} kept of {n}  |probs / exp(2 log|psi|_f64) - 1| "
           f"{rel.max():.2e} ({(rel / bound).max():.2f} x bound)")
     assert np.all(rel <= bound), (rel.max(), (rel / bound).max())
+
+
+# ------------------------------------------------------------------------- every family where the packed offsets round
+# A block with 5 or 3 outputs (amplitude spin symmetry, -phase_sym) has a float count that is no multiple of 4, so every
+# per-pair offset of the packed copies is rounded: 16-unit blocks at P = 2 and 3, each of the five kinds of handle.  (The single
+# phase MLP is no set of per-pair blocks: it keeps the published widths, whose kernel forms test_forward_f64_gpu.py holds.)
+SMALL = {"single": {}, "deep": dict(amp_layers=2),
+         "agg": dict(aggregate=True, phase_hidden=(16,)), "aggdeep": dict(aggregate=True, amp_layers=2, phase_hidden=(16, 16)),
+         "comb": dict(combined=True)}
+SMALL_KERNEL = {"single": "phase_kernel", "deep": "amp_deep_kernel<1, L=2>", "agg": "agg_finish_kernel",
+                "aggdeep": "agg_deep_kernel<1, L=2>", "comb": "comb_head_kernel"}
+SMALL_CASES = [(n, f) for n in ("H2", "syn6_2_1") for f in SMALL]
+
+
+def _small_net(name, family):
+    return gr.sector_net(name, seed=_P(name), amp_hidden=16, phase_sym=True, **SMALL[family])
+
+
+@pytest.mark.parametrize("name,family", SMALL_CASES)
+def test_small_blocks_forward_against_float64(name, family):
+    """test_forward_against_float64's bounds on the whole space plus unphysical keys; the family's own kernels ran."""
+    _threads()
+    hil, wf = _small_net(name, family)
+    fused = wf.fused()
+    assert fused is not None
+    m = wf.model
+    assert m._n_out_amp == 5 and m._n_out_phase == 3
+    P, L = hil.N // 2, len(m.amp_layers[0].linears()) - 1
+    keys = np.sort(np.concatenate([_whole(hil), _unphysical(hil, 4, 7)]))
+    _, wf64 = gr.f64_copy(wf)
+    want = gr.log_psi_f64(wf64, _states(hil, keys))
+    assert not np.isnan(want).any()
+    k_d = _kdev(keys)
+    lp = fused.log_psi(k_d).clone()
+    ran = fused.last_kernel()
+    bad, e0, e1, r = _compare(lp.cpu().numpy(), want, P * L, np.abs(want[:, 1]).max())
+    lpt, _ = fused.forward_saved(k_d)
+    print(f"[small forward {name} P={P} {family}] M={len(keys)} {ran}  |HIP - f64| log {e0:.2e} phase {e1:.2e} ({r:.2f} x bound)")
+    assert SMALL_KERNEL[family] in ran, ran
+    assert torch.equal(lpt, lp), "forward_saved differs from naqs_net_logpsi"
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("name,family", SMALL_CASES)
+def test_small_blocks_backward_against_float64(name, family):
+    _check_backward(f"{name} {family}", *_small_net(name, family))
+
+
+@pytest.mark.parametrize("name,family", SMALL_CASES)
+def test_small_blocks_sampler_probs(name, family):
+    _check_sampler_probs(f"{name} {family}", *_small_net(name, family))
 
 
 def _chi2(obs, p):
