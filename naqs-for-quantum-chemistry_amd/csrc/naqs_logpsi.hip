@@ -578,6 +578,18 @@ __device__ __forceinline__ void mlp_accumulate_h(const ushort_t *__restrict__ a_
 // scales of one layer in the f16x2 format (all 1 for bf16x3, which carries unscaled values)
 struct LayerScale { float c = 1.0f, sn = 1.0f, isn = 1.0f; };
 
+// A hidden layer whose N_pad is an odd multiple of 16 (widths 1..16, 33..48, ... 481..496): the next layer contracts over
+// Kh_pad = N_pad + 16 columns (K rounds up to the 32-wide MFMA chunk), and no tile writes the 16 columns in between.  They
+// would keep what the LDS held before — the prologue's or the K-split arm's f32 scratch, whose halves read as f16 / bf16 can
+// be Inf or NaN, and Inf x (zero-padded weight) = NaN — so they are zeroed in every plane.  Called between the barrier
+// that ends the reads of the layer's input and the one that ends its write-back; ldh >= Kh_pad + 8 (layout_phase_mlp).
+template <int RB, int FMT>
+__device__ __forceinline__ void mlp_zero_gap_h(ushort_t *__restrict__ planes, int ldh, int N_pad, int tid) {
+    constexpr int BM = RB * 16, NP = fmt_planes<FMT>::value;
+    for (int e = tid; e < NP * BM * 2; e += PH_THREADS)      // (plane, row) e >> 1, eight columns each
+        *reinterpret_cast<uint4 *>(planes + (e >> 1) * ldh + N_pad + 8 * (e & 1)) = make_uint4(0u, 0u, 0u, 0u);
+}
+
 // write-back of a wide hidden layer: the accumulators (+ bias, ReLU) go back to the LDS tile as the format's planes.
 // FMT 2: the planes hold sn * h, computed as max(acc * c + sn * b, 0) (c, sn powers of two: the same rounding as the unscaled
 // sum); bvs arrive pre-scaled.
@@ -674,6 +686,7 @@ __device__ __forceinline__ void mlp_writeback_h(ushort_t *__restrict__ planes, i
             }
         }
     }
+    if (N_pad & 16) mlp_zero_gap_h<RB, FMT>(planes, ldh, N_pad, wave * WAVE + lane);
     __syncthreads();
 }
 
@@ -732,6 +745,7 @@ __device__ __forceinline__ void mlp_layer_h(ushort_t *__restrict__ planes, int l
             }
         }
         __syncthreads();
+        if (!last) mlp_zero_gap_h<RB, FMT>(planes, ldh, N_pad, wave * WAVE + lane);   // columns 16..31 held part[]
 #pragma unroll
         for (int u = 0; u < PER; ++u) {
             const int t = u * PH_THREADS + wave * WAVE + lane;
@@ -2004,7 +2018,7 @@ static int net_alloc(naqs_net *net) {
     if (st != NAQS_OK || !mlp) return st;
     st = dev_alloc(&net->d_wh, net->wh_elems);
     if (st != NAQS_OK) return st;
-    const int lds_max = 4 * 16 * d.ld * (int)sizeof(float);
+    const int lds_max = 4 * 16 * std::max(d.ld, PH_WAVES * 16) * (int)sizeof(float);    // (PH_WAVES * 16: the K-split arm's partial tiles)
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&phase_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max / 4);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&phase_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max / 2);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&phase_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max / 4 * 3);
@@ -2693,6 +2707,7 @@ int naqs::net_logpsi_impl(naqs_net *net, int64_t M, const uint64_t *keys_dev, fl
     const int rb = sel.rb;
     const int bm = rb * 16;
     const unsigned grid = (unsigned)((M + bm - 1) / bm);
+    const size_t ksplit_scratch = (size_t)PH_WAVES * bm * 16 * sizeof(float);
     float2 *out = reinterpret_cast<float2 *>(logpsi_dev);
     WsSplit split{nullptr, 0u, net->ctl, spec ? spec->U : nullptr, spec ? spec->P : 0, naqs::SampleFinishJob{}};
     const bool host_fin = spec && spec->host_finish && net->fin_pending;
@@ -2764,7 +2779,9 @@ int naqs::net_logpsi_impl(naqs_net *net, int64_t M, const uint64_t *keys_dev, fl
 #undef NAQS_WS_LAUNCH
         if (hosted) net->fin_pending = false;             // (workgroup 0 of that launch is the sampler's finish job)
     } else if (use_h) {
-        const size_t lds = std::max(rb * lds_h16, amp_in_phase ? amp_scratch : (size_t)0);
+        // (the K-split arm of a <= 16-output layer — every network's last — keeps PH_WAVES partial tiles of [bm][16] floats in the tile:
+        //  more than the planes of a network whose widest layer is below ~120 columns)
+        const size_t lds = std::max(std::max(rb * lds_h16, amp_in_phase ? amp_scratch : (size_t)0), ksplit_scratch);
 #define NAQS_PH_LAUNCH(RB, FMT)                                                                                                         \
         do {                                                                                                                            \
             if (save.x != nullptr) NAQS_KLAUNCH((phase_kernel_h<RB, true, FMT>), dim3(grid), dim3(PH_THREADS), lds, s, d, net->d_w, net->d_wh, M, keys_dev, net->d_scratch, out, feed, save_dbg, wamp, net->d_scales); \
@@ -2786,7 +2803,7 @@ int naqs::net_logpsi_impl(naqs_net *net, int64_t M, const uint64_t *keys_dev, fl
         }
 #undef NAQS_PH_LAUNCH
     } else {
-        const size_t lds = (size_t)bm * d.ld * sizeof(float);
+        const size_t lds = std::max((size_t)bm * d.ld * sizeof(float), ksplit_scratch);
         switch (rb) {
             case 1: NAQS_KLAUNCH(phase_kernel<1>, dim3(grid), dim3(PH_THREADS), lds, s, d, net->d_w, M, keys_dev, net->d_scratch, out, feed); break;
             case 2: NAQS_KLAUNCH(phase_kernel<2>, dim3(grid), dim3(PH_THREADS), lds, s, d, net->d_w, M, keys_dev, net->d_scratch, out, feed); break;

@@ -317,12 +317,13 @@ def _check_sampler_probs(name, hil, wf):
 
 # ------------------------------------------------------------------------- every family where the packed offsets round
 # A block with 5 or 3 outputs (amplitude spin symmetry, -phase_sym) has a float count that is no multiple of 4, so every
-# per-pair offset of the packed copies is rounded: 16-unit blocks at P = 2 and 3, each of the five kinds of handle.  (The single
-# phase MLP is no set of per-pair blocks: it keeps the published widths, whose kernel forms test_forward_f64_gpu.py holds.)
-SMALL = {"single": {}, "deep": dict(amp_layers=2),
+# per-pair offset of the packed copies is rounded: 16-unit blocks at P = 2 and 3, each of the five kinds of handle; the single
+# phase MLP of the two SINGLE_PHASE kinds is [16, 16] (test_phase_shapes_gpu.py holds its other widths and depths).
+SMALL = {"single": dict(phase_hidden=(16, 16)), "deep": dict(amp_layers=2, phase_hidden=(16, 16)),
          "agg": dict(aggregate=True, phase_hidden=(16,)), "aggdeep": dict(aggregate=True, amp_layers=2, phase_hidden=(16, 16)),
          "comb": dict(combined=True)}
-SMALL_KERNEL = {"single": "phase_kernel", "deep": "amp_deep_kernel<1, L=2>", "agg": "agg_finish_kernel",
+SMALL_KERNEL = {"single": "phase_kernel_h<RB=1, SAVE=0, FMT=2 (f16x2)> + amp_kernel",
+                "deep": "phase_kernel_h<RB=1, SAVE=0, FMT=2 (f16x2)> + amp_deep_kernel<1, L=2>", "agg": "agg_finish_kernel",
                 "aggdeep": "agg_deep_kernel<1, L=2>", "comb": "comb_head_kernel"}
 SMALL_CASES = [(n, f) for n in ("H2", "syn6_2_1") for f in SMALL]
 
