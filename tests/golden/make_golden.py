@@ -430,6 +430,8 @@ VARIANTS = {
     "phasesym": (dict(use_phase_spin_sym=True), None, NadeMasking.PARTIAL),
     "phasesym_agg": (dict(use_phase_spin_sym=True, aggregate_phase=True), (32, 32, 1), NadeMasking.PARTIAL),
     "combampphase": (dict(combined_amp_phase_blocks=True, aggregate_phase=True), (32, 32, 1), NadeMasking.PARTIAL),
+    # -qo 1 (experiments/_base.py:35; wavefunction.py:56-83): model pair n is orbital pair n, not the default reversal
+    "qo1": (dict(qubit_ordering=1), None, NadeMasking.PARTIAL),
 }
 PUBLISHED_CFG = {"LiH": (64, 32, 2), "H2O": (64, 32, 2), "CH2": (64, 32, 2)}        # small phase nets for the small fixtures; else 64/512x2
 SMALL_CFG = {"N2": (64, 128, 2)}                                 # keeps the fixture small where the 512-wide phase net is not the point
@@ -465,7 +467,8 @@ def gen_variant(mol, tag, seed=111, with_eloc=None):
           "cfg_masking": masking.value, "cfg_aggregate_phase": bool(over.get("aggregate_phase", False)),
           "cfg_use_amp_spin_sym": bool(over.get("use_amp_spin_sym", True)),
           "cfg_use_phase_spin_sym": bool(over.get("use_phase_spin_sym", False)),
-          "cfg_combined_amp_phase_blocks": bool(over.get("combined_amp_phase_blocks", False))}
+          "cfg_combined_amp_phase_blocks": bool(over.get("combined_amp_phase_blocks", False)),
+          "cfg_qubit_ordering": int(over.get("qubit_ordering", -1))}
     nd.update(nade_vectors(wf, opt, hil, all_keys))
     np.savez_compressed(os.path.join(OUT, f"nade_{mol}_{tag}.npz"), **nd)
     print(f"[nade] {mol}/{tag}: n_unq={len(nd['samp_keys'])} E={nd['sgd_E']:.6f} Var={nd['sgd_Var']:.6f} "
@@ -665,6 +668,8 @@ if __name__ == "__main__":
         variants()
     if which == "widen":
         widen()
+    if which == "ordering":             # python make_golden.py ordering   (nade_LiH_qo1.npz)
+        gen_variant("LiH", "qo1")
     if which == "compat":
         gen_compat_lih()
     if which == "open-shell":

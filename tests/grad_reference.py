@@ -16,7 +16,11 @@ on the CPU is an exact-arithmetic stand-in for what the HIP backward computes in
 * ``log_amp_f64``              log|psi| alone, from the amplitude blocks' conditionals (no phase MLP): the sampler's target;
 * ``conditionals_f64``         one block's four conditional probabilities for a set of prefixes (the sampler's tree nodes);
 * ``SECTORS`` / ``sector_net`` one electron sector per orbital-pair count P = 2..16 and a default-initialised network on it;
-* ``random_keys``              distinct random physical keys of any sector.
+* ``random_keys``              distinct random physical keys of any sector;
+* ``pair_ordering`` / ``relabel_keys`` / ``model_index``
+                               qubit orderings other than -1: a seeded spin-preserving pair permutation as a
+                               ``qubit2model`` list, the same model-order bits under another ordering, and the rank of a
+                               key in the sampler's (prefix, outcome) order.
 """
 import contextlib
 
@@ -220,18 +224,19 @@ def sector(name):
 
 
 def sector_net(name, device="cuda", seed=0, masking="PARTIAL", aggregate=False, phase_sym=False, amp_layers=1, amp_hidden=64,
-               phase_hidden=(512, 512), combined=False):
+               phase_hidden=(512, 512), combined=False, qubit_ordering=-1):
     """(hilbert, network) on sector ``name``: default-initialised from ``seed``; by default the published shape (amplitude
     width 64, one phase MLP [512, 512], amplitude spin symmetry, PARTIAL masking).  ``aggregate``: one phase block of
     ``phase_hidden`` per pair (run.py's default ansatz); ``amp_layers``: hidden layers per amplitude block; ``combined``: -comb_amp_phase (the
-    last block's output layer carries the phase rows)."""
+    last block's output layer carries the phase rows); ``qubit_ordering``: -1, +1 or a ``qubit2model`` list (the weights
+    drawn from ``seed`` do not depend on it)."""
     from naqs_amd.hilbert import Encoding, Hilbert
     from naqs_amd.nade import NadeMasking
     from naqs_amd.wavefunction import NAQSComplex_NADE_orbitals
     _, N, na, nb, _ = sector(name)
     hil = Hilbert.get(N, na, nb, encoding=Encoding.SIGNED)
     torch.manual_seed(seed)
-    wf = NAQSComplex_NADE_orbitals(hil, device=device, qubit_ordering=-1, masking=NadeMasking[masking],
+    wf = NAQSComplex_NADE_orbitals(hil, device=device, qubit_ordering=qubit_ordering, masking=NadeMasking[masking],
                                    amp_hidden_size=[amp_hidden] * amp_layers, phase_hidden_size=list(phase_hidden),
                                    use_amp_spin_sym=True, use_phase_spin_sym=phase_sym, aggregate_phase=aggregate,
                                    combined_amp_phase_blocks=combined, n_alpha_electrons=na, n_beta_electrons=nb)
@@ -251,3 +256,49 @@ def random_keys(hil, M, seed):
         kb = (np.uint64(1) << (2 * b[:, :nb] + 1).astype(np.uint64)).sum(1, dtype=np.uint64)
         keys = np.unique(np.concatenate([keys, ka | kb]))
     return rs.permutation(keys)[:M]
+
+
+def pair_ordering(P, seed):
+    """A ``qubit2model`` list [2 p, 2 p + 1 for p in pi] of a seeded permutation pi of the P orbital pairs: spin preserving
+    (alpha stays on even model positions), and neither the identity (ordering +1) nor the reversal (ordering -1)."""
+    assert P >= 3, "two pairs have no permutation besides the identity and the reversal"
+    rs = np.random.RandomState(seed)
+    while True:
+        pi = rs.permutation(P)
+        if not (np.array_equal(pi, np.arange(P)) or np.array_equal(pi, np.arange(P)[::-1])):
+            break
+    assert sorted(pi.tolist()) == list(range(P))
+    assert pi.tolist() != list(range(P)) and pi.tolist() != list(range(P))[::-1]
+    return [int(q) for p in pi for q in (2 * p, 2 * p + 1)]
+
+
+def q2m_of(ordering, N):
+    """The ``qubit2model`` list of ordering -1 / +1 (wavefunction.py:78-85), or the list itself."""
+    if isinstance(ordering, int):
+        assert ordering in (1, -1)
+        return list(range(N)) if ordering == 1 else [q for p in range(N // 2 - 1, -1, -1) for q in (2 * p, 2 * p + 1)]
+    return [int(q) for q in ordering]
+
+
+def relabel_keys(keys, q2m_from, q2m_to):
+    """Bit ``q2m_from[i]`` of each input key becomes bit ``q2m_to[i]`` of the output (uint64 [M]): the key that shows a
+    network at ordering ``q2m_to`` the model-order occupations the input shows one at ``q2m_from``."""
+    keys = np.asarray(keys).astype(np.uint64)
+    assert len(q2m_from) == len(q2m_to)
+    out = np.zeros_like(keys)
+    for f, t in zip(q2m_from, q2m_to):
+        out |= ((keys >> np.uint64(f)) & np.uint64(1)) << np.uint64(t)
+    return out
+
+
+def model_index(keys, q2m):
+    """sum_n occ_n 4^(P-1-n) with occ_n = alpha + 2 beta of model pair n (int64 [M]; P <= 16 fits): the rank of a key in
+    the (prefix, outcome) order the sampler emits its table in."""
+    keys = np.asarray(keys).astype(np.uint64)
+    P = len(q2m) // 2
+    idx = np.zeros(keys.shape, np.int64)
+    for n in range(P):
+        a = ((keys >> np.uint64(q2m[2 * n])) & np.uint64(1)).astype(np.int64)
+        b = ((keys >> np.uint64(q2m[2 * n + 1])) & np.uint64(1)).astype(np.int64)
+        idx = idx * 4 + a + 2 * b
+    return idx

@@ -84,7 +84,8 @@ def _c2(e):
 
 # ---------------------------------------------------------------------------------------------------------------- (a)
 FUSED_ALL = ["LiH", "H2O", "N2", "LiH_noampsym", "LiH_fullmask", "N2_noampsym", "N2_nomask", "N2_0.75_fullmask", "N2_2.25_fullmask",
-             "LiH_aggphase", "N2_aggphase", "LiH_phasesym", "LiH_phasesym_agg", "CH2_noampsym", "CH2_fullmask_noampsym"]
+             "LiH_aggphase", "N2_aggphase", "LiH_phasesym", "LiH_phasesym_agg", "CH2_noampsym", "CH2_fullmask_noampsym",
+             "LiH_qo1"]
 
 
 def test_fused_list_covers_the_variant_suite():

@@ -16,7 +16,7 @@ FIXTURES = sorted(os.path.basename(f)[5:-4] for f in glob.glob(os.path.join(GOLD
 
 
 def test_every_fixture_is_listed():
-    assert len(FIXTURES) == 16 and "N2" in FIXTURES and "CH2_noampsym" in FIXTURES
+    assert len(FIXTURES) == 17 and "N2" in FIXTURES and "CH2_noampsym" in FIXTURES and "LiH_qo1" in FIXTURES
 
 
 @pytest.mark.parametrize("fix", FIXTURES)

@@ -24,7 +24,8 @@ def make_wf(mol, z, device="cpu", masking=None):
     sym = bool(z["cfg_use_amp_spin_sym"]) if "cfg_use_amp_spin_sym" in z.files else True
     psym = bool(z["cfg_use_phase_spin_sym"]) if "cfg_use_phase_spin_sym" in z.files else False
     comb = bool(z["cfg_combined_amp_phase_blocks"]) if "cfg_combined_amp_phase_blocks" in z.files else False
-    wf = NAQSComplex_NADE_orbitals(hil, qubit_ordering=-1, masking=masking,
+    qo = int(z["cfg_qubit_ordering"]) if "cfg_qubit_ordering" in z.files else -1
+    wf = NAQSComplex_NADE_orbitals(hil, qubit_ordering=qo, masking=masking,
                                    amp_hidden_size=[int(z["cfg_n_hid"])],
                                    phase_hidden_size=[int(z["cfg_n_hid_phase"])] * int(z["cfg_n_layer_phase"]),
                                    use_amp_spin_sym=sym, use_phase_spin_sym=psym, aggregate_phase=agg,

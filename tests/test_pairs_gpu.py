@@ -58,8 +58,8 @@ def _P(name):
     return gr.sector(name)[1] // 2
 
 
-def _net(name, variant="base", seed=None):
-    return gr.sector_net(name, seed=_P(name) if seed is None else seed, **VARIANTS[variant])
+def _net(name, variant="base", seed=None, **kw):
+    return gr.sector_net(name, seed=_P(name) if seed is None else seed, **VARIANTS[variant], **kw)
 
 
 def _kdev(keys):
@@ -553,10 +553,11 @@ def test_launch_fusions_change_nothing(name, monkeypatch):
 LOOP = ["H2", "H2_6-31G", "syn10_3_2"]          # P = 2, 4, 5 (the first P whose update launch packs head pairs)
 
 
-def _opt(name, tmp, **kw):
+def _opt(name, tmp, net_kw=None, **kw):
+    """``net_kw``: passed to the network (``qubit_ordering``: test_qubit_ordering_gpu.py); ``kw``: to the optimiser."""
     from naqs_amd.optimizer import PartialSamplingOptimizer
     from test_optimizer import ADAM
-    hil, wf = _net(name)
+    hil, wf = _net(name, **(net_kw or {}))
     _, N, na, nb, _ = gr.sector(name)
     args = dict(n_samples=100000, n_samples_max=1e12, n_unq_samples_min=2, n_unq_samples_max=1e5, log_exact_energy=False,
                 wavefunction=wf, qubit_hamiltonian=_row_ham(name, None), pre_compute_H=False, n_electrons=na + nb,
@@ -570,17 +571,21 @@ def _opt(name, tmp, **kw):
 @pytest.mark.parametrize("name", LOOP)
 def test_library_loop_equals_step_by_step(name, tmp_path, monkeypatch):
     """naqs_vmc_run over 20 steps against one naqs_vmc_step per step: energies, sample counts and parameters bit for bit."""
+    _loop_equals_step_by_step(name, tmp_path, monkeypatch, 20)
+
+
+def _loop_equals_step_by_step(name, tmp_path, monkeypatch, steps, **net_kw):
     from naqs_amd.optimizer import LogKey
     runs = {}
     for mode in ("1", "0"):
         monkeypatch.setenv("NAQS_TRAIN_RUN", mode)
-        hil, wf, opt = _opt(name, tmp_path / mode)
+        hil, wf, opt = _opt(name, tmp_path / mode, net_kw=net_kw)
         assert opt._can_onecall() and opt._can_run_in_library() == (mode == "1")
-        opt.run(n_epochs=20, save_freq=None, save_final=False, output_freq=10 ** 9)
+        opt.run(n_epochs=steps, save_freq=None, save_final=False, output_freq=10 ** 9)
         runs[mode] = (np.array(opt.log[LogKey.E_LOC]), np.array(opt.log[LogKey.N_UNIQUE_SAMP]), wf.flatten_parameters().clone())
     a, b = runs["1"], runs["0"]
-    print(f"[library loop {name}] 20 steps, <E> {a[0][0, 1]:.6f} -> {a[0][-1, 1]:.6f}")
-    assert len(a[0]) == 20 and np.isfinite(a[0]).all()
+    print(f"[library loop {name} {net_kw or ''}] {steps} steps, <E> {a[0][0, 1]:.6f} -> {a[0][-1, 1]:.6f}")
+    assert len(a[0]) == steps and np.isfinite(a[0]).all()
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and torch.equal(a[2], b[2])
 
 
@@ -590,13 +595,16 @@ def test_forward_after_library_training_steps(name, overlap, tmp_path, monkeypat
     """test_forward_f64_gpu.py's trained-network check at P <= 5 (the re-pack of the first pairs goes ahead of a head-less
     sampler there): after 50 library steps with no refresh, the forward of the whole space against the float64 copy of the
     current parameters in every NAQS_PACK_OVERLAP mode."""
-    import test_forward_f64_gpu as tf
+    _forward_after_training(name, overlap, tmp_path, monkeypatch, 50)
+
+
+def _forward_after_training(name, overlap, tmp_path, monkeypatch, steps, **net_kw):
     _threads()
     monkeypatch.setenv("NAQS_PACK_OVERLAP", overlap)
-    hil, wf, opt = _opt(name, tmp_path)
+    hil, wf, opt = _opt(name, tmp_path, net_kw=net_kw)
     assert opt._can_onecall()
     p0 = wf.flatten_parameters().clone()
-    opt.run(n_epochs=50, save_freq=None, save_final=False, output_freq=10 ** 9)
+    opt.run(n_epochs=steps, save_freq=None, save_final=False, output_freq=10 ** 9)
     torch.cuda.synchronize()
     fused = wf._fused
     assert fused is not None and fused is not False
@@ -606,7 +614,7 @@ def test_forward_after_library_training_steps(name, overlap, tmp_path, monkeypat
     want = gr.log_psi_f64(wf64, _states(hil, keys))
     lp = fused.log_psi(_kdev(keys))
     bad, e0, e1, r = _compare(lp.cpu().numpy(), want, hil.N // 2, np.abs(want[:, 1]).max())
-    print(f"[trained {name} NAQS_PACK_OVERLAP={overlap}] M={len(keys)} {fused.last_kernel()}  |HIP - f64| log {e0:.2e} "
+    print(f"[trained {name} {net_kw or ''} NAQS_PACK_OVERLAP={overlap}] M={len(keys)} {fused.last_kernel()}  |HIP - f64| log {e0:.2e} "
           f"phase {e1:.2e} ({r:.2f} x bound)")
     assert not bad, bad
 

@@ -17,8 +17,10 @@ from test_nade import ELECTRONS, make_wf
 VARIANT_FIXTURES = ["LiH_aggphase", "LiH_noampsym", "LiH_fullmask", "N2_aggphase", "N2_noampsym", "N2_nomask",
                     "N2_0.75_fullmask", "N2_2.25_fullmask",
                     # open shell restricted to m_s = S (experiments/_base.py:101-123): CH2 triplet, 5 alpha / 3 beta electrons
-                    "CH2_noampsym", "CH2_fullmask_noampsym"]
-TAGS = ["fullmask_noampsym", "aggphase", "noampsym", "nomask", "fullmask", "phasesym_agg", "phasesym", "combampphase"]
+                    "CH2_noampsym", "CH2_fullmask_noampsym",
+                    # -qo 1 (experiments/_base.py:35): model pair n is orbital pair n (make_golden.py `ordering`)
+                    "LiH_qo1"]
+TAGS = ["fullmask_noampsym", "aggphase", "noampsym", "nomask", "fullmask", "phasesym_agg", "phasesym", "combampphase", "qo1"]
 # round 4: the live options no published script uses — -phase_sym (nade.py:281, 593-610) and -comb_amp_phase
 # (nade.py:257-262, 294-303) — as PyTorch modules, against the reference's own vectors (make_golden.py `widen`)
 WIDEN_FIXTURES = ["LiH_phasesym", "LiH_phasesym_agg", "LiH_combampphase"]
@@ -63,7 +65,7 @@ def test_variant_log_psi_matches_reference(fix):
 
 
 @pytest.mark.parametrize("fix", ["LiH_aggphase", "LiH_noampsym", "LiH_fullmask", "N2_aggphase", "N2_noampsym",
-                                 "CH2_noampsym", "CH2_fullmask_noampsym"] + WIDEN_FIXTURES)
+                                 "CH2_noampsym", "CH2_fullmask_noampsym", "LiH_qo1"] + WIDEN_FIXTURES)
 def test_variant_sgd_step_matches_reference_step(fix, tmp_path, monkeypatch):
     """energy, variance, loss, every gradient and every parameter after the reference's own _SGD_step."""
     import oracle_backend

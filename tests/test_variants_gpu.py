@@ -26,7 +26,9 @@ FUSED = ["LiH_noampsym", "LiH_fullmask", "N2_noampsym", "N2_nomask", "N2_0.75_fu
          # -phase_sym with the single phase block (round 5): spin-ordered inputs, 3 outputs, the sign shift — on the kernels
          "LiH_phasesym", "LiH_phasesym_agg",
          # open shell restricted to m_s = S (experiments/_base.py:101-123): CH2 triplet, 5 alpha / 3 beta electrons, no amp symmetry
-         "CH2_noampsym", "CH2_fullmask_noampsym"]
+         "CH2_noampsym", "CH2_fullmask_noampsym",
+         # -qo 1: model pair n is orbital pair n (every key-bit site of the kernels away from the default reversal)
+         "LiH_qo1"]
 EAGER = []
 
 
