@@ -303,6 +303,34 @@ int naqs_net_logpsi(naqs_net_t *net, int64_t M, const uint64_t *keys_dev, float 
 int naqs_logpsi_eloc(naqs_net_t *net, naqs_ham_t *ham, int64_t M, const uint64_t *keys_dev,
                      const double *w_dev, float *logpsi_dev, double *eloc_dev, double *out4_dev, void *stream);
 
+/*
+ * Exact local energies of table rows [row_begin, row_begin + n_rows) in ONE call, device-resident: the training-time form of
+ * the branch the reference leaves as `raise NotImplementedError()` (src/optimizer/energy.py:227-235, 250-258).  By definition
+ * the sequence
+ *   naqs_ham_connected(ham, M, keys, row_begin, n_rows, capacity, keys + M, &count)
+ *   naqs_net_logpsi(net, count, keys + M, logpsi + M)
+ *   naqs_eloc_reduced(ham, M + count, keys, logpsi, NAQS_LOGPSI_F32, row_begin, n_rows, w, eloc, out4)
+ * with eloc_dev and out4_dev bit for bit what that sequence gives: the connected set is appended IN PLACE behind the table
+ * (no copy, no concatenation, no sort: a row's hit set and summation order depend neither on what else the table holds nor
+ * on its order, and the forward is row-independent), and the only thing the host learns is the count — published to a mapped
+ * host word by a one-thread launch behind connected_kernel and read by a bounded poll (NAQS_SPIN_WAIT=0: the stream is
+ * waited for instead), the way naqs_vmc_step learns M.  No workgroup waits for another.
+ *
+ * keys_dev   [M + capacity]: rows < M the table (input, unchanged); on return rows [M, M + count) hold the connected set
+ *            of the range, in any order
+ * logpsi_dev float [M + capacity][2]: rows < M input — log psi of the table from any forward of the handle's current
+ *            parameters; rows [M, M + count) output, from the handle's inference forward (every family a handle can be)
+ * eloc_dev   double [n_rows][2]
+ * w_dev [n_rows], out4_dev [4]: both or neither; out4_dev <- the four weighted sums of the produced rows
+ * info_host[0] = count (on overflow a lower bound, as in naqs_ham_connected), info_host[1] = 1 iff count > capacity.
+ * On overflow the call returns NAQS_OK, nothing after the connected kernel is launched and eloc_dev, out4_dev and logpsi_dev
+ * are untouched.  NAQS_ERR_UNSUPPORTED when M + count exceeds the 2^24 - 1 rows an E_loc table indexes; NAQS_ERR_INVALID
+ * when net and ham do not live on the same device.
+ */
+int naqs_exact_eloc(naqs_net_t *net, naqs_ham_t *ham, int64_t M, uint64_t *keys_dev, float *logpsi_dev,
+                    int64_t row_begin, int64_t n_rows, int64_t capacity, const double *w_dev,
+                    double *eloc_dev, double *out4_dev, int64_t info_host[2], void *stream);
+
 /* HIP-event timing of the phase-MLP kernel, like naqs_prof_enable / naqs_prof_read. */
 int naqs_net_prof_enable(naqs_net_t *net, int max_records);
 int naqs_net_prof_read(naqs_net_t *net, double *total_ms, int64_t *launches);

@@ -91,5 +91,6 @@ int eloc_begin(naqs_ham *h, int64_t M, hipStream_t s, ElocFeed *feed);
 int eloc_main(naqs_ham *h, int64_t M, const ElocFeed &feed, double *eloc_dev, const double *w_dev, double *out4_dev,
               hipStream_t s);
 int ham_device(const naqs_ham *h);
+int net_device(const naqs_net *n);           // implemented in naqs_logpsi.hip
 
 }  // namespace naqs

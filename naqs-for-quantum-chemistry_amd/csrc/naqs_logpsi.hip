@@ -2831,6 +2831,8 @@ NAQS_API int naqs_net_logpsi(naqs_net_t *net, int64_t M, const uint64_t *keys_de
     return naqs::net_logpsi_impl(net, M, keys_dev, logpsi_dev, stream, none, naqs::PhaseSave{});
 }
 
+int naqs::net_device(const naqs_net *n) { return n->device; }      // for naqs_exact_eloc (naqs_hip.hip), to which the handle is opaque
+
 NAQS_API int naqs_logpsi_eloc(naqs_net_t *net, naqs_ham_t *ham, int64_t M, const uint64_t *keys_dev,
                               const double *w_dev, float *logpsi_dev, double *eloc_dev, double *out4_dev,
                               void *stream) {

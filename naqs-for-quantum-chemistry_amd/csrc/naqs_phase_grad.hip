@@ -786,15 +786,6 @@ NAQS_API int naqs_net_train_forward_eloc(naqs_net_t *net, naqs_ham_t *ham, int64
 // short spin; waking up costs tens of microseconds during which the GPU has nothing to do): it sees them about a
 // microsecond after the store and queues the forward pass while the sampler's last launches are still running.
 // NAQS_SPIN_WAIT=0: wait for the stream instead.
-static inline void cpu_relax() {
-#if defined(__x86_64__) || defined(__i386__)
-    __builtin_ia32_pause();
-#elif defined(__aarch64__)
-    asm volatile("yield");
-#else
-    std::this_thread::yield();
-#endif
-}
 struct AfterSampler {          // what the caller queues behind the sampler's launches before the host starts waiting for M
     virtual int operator()() = 0;  // (the sampler's finish job is still pending — net->fin_job — and may ride in what is queued here)
     virtual ~AfterSampler() = default;
@@ -803,7 +794,6 @@ static int sample_and_wait(naqs_net_t *net, int64_t n_samples, uint64_t seed, in
                            int64_t *counts_dev, float *probs_dev, double *weights_dev, hipStream_t s, int64_t out[2],
                            int64_t *info_dev = nullptr, AfterSampler *after = nullptr) {
     // info_dev: where the sampler leaves its plain (M, overflow) words on the device (default: the handle's own two words)
-    static const bool spin = [] { const char *e = getenv("NAQS_SPIN_WAIT"); return !e || atoi(e) != 0; }();
     int st0 = naqs::net_info_alloc(net);
     if (st0 != NAQS_OK) return st0;
     const int64_t seq = ++net->info_seq;
@@ -830,22 +820,8 @@ static int sample_and_wait(naqs_net_t *net, int64_t n_samples, uint64_t seed, in
         if (st2 != NAQS_OK) return st2;
     }
     volatile int64_t *h = net->h_info;
-    if (spin) {
-        // bounded: after ~2 s of polling (a sampler call is < 1 ms) the wait falls back to the stream's own completion signal
-        const auto t0 = std::chrono::steady_clock::now();
-        for (uint64_t it = 1; h[2] != seq; ++it) {
-            if ((it & 0x3FFF) == 0) {                      // every ~0.2 ms: is the stream still alive?
-                const hipError_t q = hipStreamQuery(s);
-                if (q == hipSuccess) break;
-                if (q != hipErrorNotReady) return NAQS_ERR_HIP;
-                if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) { HIP_TRY(hipStreamSynchronize(s)); break; }
-            }
-            cpu_relax();
-        }
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    } else {
-        HIP_TRY(hipStreamSynchronize(s));
-    }
+    st = naqs::host_wait_published(&net->h_info[2], seq, s);      // bounded poll, or the stream (naqs_poll.hpp)
+    if (st != NAQS_OK) return st;
     { const int pc = naqs::poll_check(net->poll); if (pc != NAQS_OK) return pc; }      // a look-back wait that gave up (naqs_poll.hpp)
     if (h[2] != seq) return NAQS_ERR_HIP;                   // the stream drained and nothing was published
     out[0] = h[0];

@@ -15,7 +15,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <cstdint>
+#include <cstdlib>
+#include <thread>
+
+#include "naqs_common.hpp"
 
 namespace naqs {
 
@@ -71,6 +76,42 @@ __device__ __forceinline__ bool poll_tagged(const unsigned long long *src, const
     }
 }
 #endif
+
+// The host's side of a hand-over through MAPPED HOST memory (publish_info's (M, overflow, call number) of the sampler, the
+// connected set's (count, call number) of naqs_exact_eloc): wait until `*word == want`.  hipStreamSynchronize goes to sleep on the
+// queue's completion signal after a short spin and waking up costs tens of microseconds during which the GPU has nothing to do;
+// polling sees the store about a microsecond after it.  Bounded: every 2^14 looks (~0.2 ms) the stream is asked whether it is
+// still alive (drained: leave; failed: NAQS_ERR_HIP), and after 2 s the wait falls back to the stream's own completion.
+// NAQS_SPIN_WAIT=0: wait for the stream instead.  NAQS_OK does not say the word arrived — the caller compares once more.
+inline void host_cpu_relax() {
+#if defined(__x86_64__) || defined(__i386__)
+    __builtin_ia32_pause();
+#elif defined(__aarch64__)
+    asm volatile("yield");
+#else
+    std::this_thread::yield();
+#endif
+}
+inline int host_wait_published(const int64_t *word, const int64_t want, hipStream_t s) {
+    static const bool spin = [] { const char *e = std::getenv("NAQS_SPIN_WAIT"); return !e || std::atoi(e) != 0; }();
+    volatile const int64_t *w = word;
+    if (spin) {
+        const auto t0 = std::chrono::steady_clock::now();
+        for (uint64_t it = 1; *w != want; ++it) {
+            if ((it & 0x3FFF) == 0) {
+                const hipError_t q = hipStreamQuery(s);
+                if (q == hipSuccess) break;
+                if (q != hipErrorNotReady) { g_last_hip = q; return NAQS_ERR_HIP; }
+                if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) { HIP_TRY(hipStreamSynchronize(s)); break; }
+            }
+            host_cpu_relax();
+        }
+        __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    } else {
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return NAQS_OK;
+}
 
 // host side (naqs_hip.hip).  Round 6: a control block and an error word PER HANDLE that launches waiting kernels (every network
 // handle), not per device — two runs share a GPU in the farm (experiments.run --per-gpu 2), and with one word per device the

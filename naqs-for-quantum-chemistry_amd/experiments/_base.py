@@ -70,6 +70,8 @@ _SWITCHES = [
     (("-v", "--verbose"), "verbose", lambda k: k["verbose"], "Verbose logging."),
     (("-exact_eloc",), "exact_eloc", lambda k: k["exact_eloc"],
      "After training, estimate the energy from a fresh sample with exact local energies (psi on every connected state)."),
+    (("-train_exact_eloc",), "train_exact_eloc", lambda k: k["train_exact_eloc"],
+     "Train on exact local energies (psi on every connected state)"),
 ]
 _DEFAULTS = dict(molecule="molecules/H2", hamiltonian_fname=None, out=None, number=1, qubit_ordering=-1, lr=-1,
                  lr_lut=1e-2, n_samps=1e6, n_samps_max=1e12, n_unq_samps_min=50000, n_unq_samps_max=1e5,
@@ -78,7 +80,7 @@ _DEFAULTS = dict(molecule="molecules/H2", hamiltonian_fname=None, out=None, numb
                  load_hamiltonian=False, overwrite_hamiltonian=False, presolve_hamiltonian=False,
                  pretrained_model_loc=None, cont=False, n_excitations_max=-1, comb_amp_phase=False,
                  use_amp_spin_sym=True, use_phase_spin_sym=False, aggregate_phase=True, restrict_H=True,
-                 reset_opt=False, verbose=False, seed=-1, exact_eloc=False)
+                 reset_opt=False, verbose=False, seed=-1, exact_eloc=False, train_exact_eloc=False)
 
 
 def get_parser(**overrides):
@@ -175,7 +177,8 @@ def _run(molecule_fname, hamiltonian_fname, exp_name, num_experiments, pretraine
          reset_optimizer, qubit_ordering, masking, lr, lr_lut, n_samps, n_samps_max, n_unq_samps_min, n_unq_samps_max,
          reweight_samples_by_psi, n_train, n_pretrain, output_freq, save_freq, n_lut, n_hid, n_layer, n_hid_phase,
          n_layer_phase, n_excitations_max, comb_amp_phase, use_amp_spin_sym, use_phase_spin_sym, aggregate_phase,
-         use_restrictedH, loadH, presolveH, overwrite_pauli_hamiltonian, verbose, seed, device=None, exact_eloc=False):
+         use_restrictedH, loadH, presolveH, overwrite_pauli_hamiltonian, verbose, seed, device=None, exact_eloc=False,
+         train_exact_eloc=False):
     # (-phase_sym runs on the HIP kernels since round 5, -comb_amp_phase with -single_phase and -n_layer 1 too (naqs_net_create_combined;
     # with the aggregate phase or deeper blocks as PyTorch modules on the device) — no published script uses either; -n_pretrain is
     # OptimizerBase.pre_flatten; -weight_by_psi is accepted and, as in the reference, has no effect on this optimiser:
@@ -194,7 +197,7 @@ def _run(molecule_fname, hamiltonian_fname, exp_name, num_experiments, pretraine
                            continue_experiment, reset_optimizer, qubit_ordering, masking, lr, lr_lut, n_samps, n_samps_max,
                            n_unq_samps_min, n_unq_samps_max, n_train, n_pretrain, output_freq, save_freq, n_lut, n_hid, n_layer,
                            n_hid_phase, n_layer_phase, comb_amp_phase, use_amp_spin_sym, use_phase_spin_sym, aggregate_phase,
-                           use_restrictedH, presolveH, verbose, seed, device, exact_eloc)
+                           use_restrictedH, presolveH, verbose, seed, device, exact_eloc, train_exact_eloc)
     finally:
         if locked[0]:
             _SETUP_LOCK.release()
@@ -207,7 +210,7 @@ def _run_locked(locked, molecule_fname, hamiltonian_fname, exp_name, num_experim
                 reset_optimizer, qubit_ordering, masking, lr, lr_lut, n_samps, n_samps_max, n_unq_samps_min, n_unq_samps_max,
                 n_train, n_pretrain, output_freq, save_freq, n_lut, n_hid, n_layer, n_hid_phase, n_layer_phase, comb_amp_phase,
                 use_amp_spin_sym, use_phase_spin_sym, aggregate_phase, use_restrictedH, presolveH, verbose, seed, device,
-                exact_eloc=False):
+                exact_eloc=False, train_exact_eloc=False):
     seed = set_global_seed(_agree_on_seed(seed))
     molecule, qubit_hamiltonian = load_molecule(molecule_fname, hamiltonian_fname=hamiltonian_fname, verbose=True)
     N = molecule.n_qubits
@@ -259,7 +262,8 @@ def _run_locked(locked, molecule_fname, hamiltonian_fname, exp_name, num_experim
             normalize_grads=False, grad_clip_factor=None, grad_clip_memory_length=50, optimizer=torch.optim.Adam,
             optimizer_args=[{'lr': lr, 'betas': (0.9, 0.99), 'weight_decay': 0, 'eps': 1e-15, 'amsgrad': False},
                             {'lr': lr_lut}],
-            save_loc=exp_name_i, pauli_hamiltonian_dtype=np.float64, verbose=verbose, seed=seed + i)
+            save_loc=exp_name_i, pauli_hamiltonian_dtype=np.float64, verbose=verbose, seed=seed + i,
+            exact_local_energies=train_exact_eloc)
         print("\n---System summary---\n")
         print(f"Size of restricted subspace : {hilbert.size}.")
         print("Qubit ordering in model :", wavefunction.qubit2model_permutation)
@@ -307,7 +311,10 @@ def _summarise(opt, molecule, exp_name, eig_val, n_unq, train_time, exact=None):
     window = min(50, len(e))
     final = float(e[-window:].mean()) if len(e) else float("nan")
     fci = molecule.fci_energy
+    estimator = ("exact local energies (psi on every connected state)" if getattr(opt, "exact_local_energies", False)
+                 else "truncated local energies (un-sampled amplitudes count as zero)")
     lines = [f"molecule : {molecule.name}", f"n_steps : {opt.n_steps}", f"training time (s) : {train_time:.1f}",
+             f"trained on : {estimator}",
              f"final <E_loc> (mean of last {window}) : {final:.8f}",
              f"min <E_loc> : {float(e.min()) if len(e) else float('nan'):.8f}",
              f"sampled-subspace diagonalisation ({n_unq} states) : {eig_val:.8f}",
@@ -451,7 +458,7 @@ def _run_job(args, molecule_fname, seed):
     masking = NadeMasking.NONE if args.no_mask_psi else (NadeMasking.FULL if args.full_mask_psi else NadeMasking.PARTIAL)
     print(f"Running experimental script: {__file__}\nResults will be saved to: {exp_name}/\n\nscript options:")
     for key, val in sorted(vars(args).items()):
-        if key == "exact_eloc" and not val:      # an opt-in of this port: without it the listing is the reference's
+        if key in ("exact_eloc", "train_exact_eloc") and not val:      # an opt-in of this port: without it the listing is the reference's
             continue
         print(f"\t{key} : {val}")
     print("")
@@ -467,7 +474,8 @@ def _run_job(args, molecule_fname, seed):
                 comb_amp_phase=args.comb_amp_phase, use_amp_spin_sym=not args.no_amp_sym,
                 use_phase_spin_sym=args.phase_sym, aggregate_phase=not args.single_phase,
                 use_restrictedH=not args.no_restrictedH, loadH=args.loadH, presolveH=args.presolveH,
-                overwrite_pauli_hamiltonian=args.overwriteH, verbose=args.verbose, seed=seed, exact_eloc=args.exact_eloc)
+                overwrite_pauli_hamiltonian=args.overwriteH, verbose=args.verbose, seed=seed, exact_eloc=args.exact_eloc,
+                train_exact_eloc=args.train_exact_eloc)
 
 
 def run(*args, **kwargs):

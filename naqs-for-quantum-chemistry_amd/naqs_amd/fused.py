@@ -184,14 +184,15 @@ class FusedLogPsi:
 
     # ---- training step without the autograd engine --------------------------------------------------------
     @torch.no_grad()
-    def forward_saved(self, keys):
+    def forward_saved(self, keys, out=None):
         """log psi [M, 2] of int64 device keys, evaluated without recording an autograd graph, plus the token
         ``backward_saved`` needs.  ``mode="hip"`` (default): ``naqs_net_train_forward`` — the inference kernels, the
-        phase activations stay in the handle.  ``mode="blas"``: HIP amplitude kernels + one addmm/relu per phase layer."""
+        phase activations stay in the handle (``out``: a contiguous float32 [M, 2] to write to).  ``mode="blas"``: HIP
+        amplitude kernels + one addmm/relu per phase layer."""
         keys = keys.contiguous()
         M = keys.shape[0]
         if self.train_mode == "hip":
-            log_psi = torch.empty((M, 2), dtype=torch.float32, device=self.device)
+            log_psi = torch.empty((M, 2), dtype=torch.float32, device=self.device) if out is None else out
             st = self._lib.naqs_net_train_forward(self._h, M, keys.data_ptr(), log_psi.data_ptr(), _stream_ptr(self.device))
             _lib.check(st, "naqs_net_train_forward")
             return log_psi, (keys, None, None)
@@ -339,6 +340,15 @@ class FusedLogPsi:
                                        _stream_ptr(self.device))
         _lib.check(st, "naqs_net_logpsi")
         return out
+
+    def exact_local_energy(self, ham, keys_buf, logpsi_buf, M, row_begin, n_rows, capacity, weights=None, out=None, sums_out=None):
+        """Exact local energies of table rows [row_begin, row_begin + n_rows) with psi of the connected states the table
+        lacks from THIS network's inference forward, in one library call (``naqs_exact_eloc``;
+        ``DevicePauliHamiltonian.exact_local_energy``).  ``logpsi_buf[:M]`` holds log psi of the table from a forward of the
+        current parameters (``forward_saved(keys, out=logpsi_buf[:M])``).
+        -> (E_loc float64 [n_rows, 2], sums float64 [4] or None, count, overflow)."""
+        return ham.exact_local_energy(self._h, keys_buf, logpsi_buf, M, row_begin, n_rows, capacity, weights=weights, out=out,
+                                      sums_out=sums_out)
 
     def log_psi_and_local_energy(self, ham, keys, weights=None, log_psi_out=None, eloc_out=None, sums_out=None):
         """keys -> (log psi float32 [M, 2], E_loc float64 [M, 2][, sums float64 [4]]) in one library call

@@ -167,6 +167,41 @@ class DevicePauliHamiltonian:
         # (bit patterns of uint64 keys: every supported key has bit 63 clear, so the signed order is the unsigned one)
         return torch.sort(out[:n]).values, n
 
+    def exact_local_energy(self, net_handle, keys_buf, logpsi_buf, M, row_begin, n_rows, capacity, weights=None, out=None,
+                           sums_out=None):
+        """Exact local energies of table rows [row_begin, row_begin + n_rows) in one library call (``naqs_exact_eloc``):
+        the connected states the table lacks are appended behind it in ``keys_buf``, ``net_handle``'s inference forward
+        writes their log psi behind the table's in ``logpsi_buf``, and the E_loc kernel runs over the union.
+
+        keys_buf   : int64 device tensor [>= M + capacity]; rows < M the table
+        logpsi_buf : float32 device tensor [>= M + capacity, 2]; rows < M log psi of the table
+        -> (E_loc float64 [n_rows, 2], sums float64 [4] or None, count, overflow).  On overflow (more than ``capacity``
+        connected states; ``count`` is then a lower bound) nothing was evaluated and ``out`` / ``sums_out`` are untouched."""
+        M, row_begin, n_rows, capacity = int(M), int(row_begin), int(n_rows), int(capacity)
+        if not (keys_buf.is_cuda and keys_buf.dtype == torch.int64 and keys_buf.is_contiguous()):
+            raise ValueError("keys_buf must be a contiguous int64 device tensor")
+        if not (logpsi_buf.is_cuda and logpsi_buf.dtype == torch.float32 and logpsi_buf.is_contiguous()):
+            raise ValueError("logpsi_buf must be a contiguous float32 device tensor")
+        if capacity < 0 or keys_buf.shape[0] < M + capacity or tuple(logpsi_buf.shape[1:]) != (2,) or logpsi_buf.shape[0] < M + capacity:
+            raise ValueError(f"buffers must hold the table and the capacity: {M} + {capacity} rows")
+        if row_begin < 0 or n_rows < 0 or row_begin + n_rows > M:
+            raise ValueError(f"rows [{row_begin}, {row_begin + n_rows}) are not rows of a table of {M}")
+        if out is None:
+            out = torch.empty((n_rows, 2), dtype=torch.float64, device=self.device)
+        w_ptr = s_ptr = None
+        if weights is not None:
+            weights = weights.to(device=self.device, dtype=torch.float64).contiguous()
+            if weights.shape[0] != n_rows:
+                raise ValueError("weights must cover exactly the produced rows")
+            if sums_out is None:
+                sums_out = torch.empty(4, dtype=torch.float64, device=self.device)
+            w_ptr, s_ptr = weights.data_ptr(), sums_out.data_ptr()
+        info = (ctypes.c_int64 * 2)()
+        st = self._lib.naqs_exact_eloc(net_handle, self._h, M, keys_buf.data_ptr(), logpsi_buf.data_ptr(), row_begin, n_rows,
+                                       capacity, w_ptr, out.data_ptr(), s_ptr, info, _stream_ptr(self.device))
+        _lib.check(st, "naqs_exact_eloc")
+        return out, (sums_out if weights is not None else None), int(info[0]), bool(info[1])
+
     # ---- H restricted to the sampled states, matrix-free ----------------------------------------
     def matvec(self, keys, v, out=None):
         """out_i = sum_j H_ij v_j over the sampled keys (``naqs_hmatvec``).  v: real [M] or complex-as-pairs [M, 2]

@@ -106,7 +106,17 @@ class OptimizerBase:
                  grad_clip_memory_length=50, optimizer=torch.optim.Adam, optimizer_args={'lr': 1e-3},
                  scheduler=None, scheduler_args=None, save_loc='./', pauli_hamiltonian_fname=None,
                  overwrite_pauli_hamiltonian=False, pauli_hamiltonian_dtype=np.float32, verbose=False, seed=None,
-                 bug_compat_full_sample_order=False):
+                 bug_compat_full_sample_order=False, exact_local_energies=False):
+        # train on exact local energies: psi evaluated on every connected state (the branch the reference leaves as
+        # ``raise NotImplementedError()``, energy.py:227-235, 250-258), instead of counting un-sampled amplitudes as zero
+        self.exact_local_energies = bool(exact_local_energies)
+        if self.exact_local_energies and bug_compat_full_sample_order:
+            raise NotImplementedError("exact local energies with bug_compat_full_sample_order: the quirk reorders the table")
+        self.exact_max_table = 2 ** 22           # rows of table + connected states per block (``_exact_local_energy``)
+        self._exact_block_rows = None            # the block length that last fitted, kept between steps
+        self._exact_bufs = None                  # (keys int64 [n], log psi float32 [n, 2]) the exact step appends to
+        # per output line of run(): (step, connected states psi was evaluated on since the last line); not a log / checkpoint key
+        self.n_connected, self._n_connected_pending = [], 0
         self.grad_clip_factor, self.grad_clip_memory_length = grad_clip_factor, int(grad_clip_memory_length)
         # opt-in reproduction of the reference's full-sample quirk (hamiltonian.py:100-105): when a batch
         # holds EVERY state of the restricted space, get_H returns H in restricted-basis order while psi stays in
@@ -278,7 +288,9 @@ class OptimizerBase:
             elif self._dist_mode == "sharded" and mode != "sharded":
                 self._check_shards()
             m = self.wavefunction.model
-            if getattr(m, "combined_amp_phase_blocks", False) and not m.aggregate_phase:
+            if self.exact_local_energies:
+                mode = "replicated"          # exact local energies: no sharded step at any table size
+            elif getattr(m, "combined_amp_phase_blocks", False) and not m.aggregate_phase:
                 mode = "replicated"          # -single_phase -comb_amp_phase: no sharded step (naqs_vmc_shard_* refuse its handles)
             elif m.aggregate_phase and len(m.amp_layers[0].linears()) > 2:
                 mode = "replicated"          # aggregate phase with -n_layer >= 2: likewise (naqs_net_create_agg_layers' handles)
@@ -440,6 +452,81 @@ class OptimizerBase:
                 lp = self.wavefunction.log_psi(self.hilbert.idx2state(keys))
         return torch.as_tensor(lp).detach().reshape(-1, 2).to(self.device, torch.float64)
 
+    def _walk_exact_blocks(self, M, row_begin, n_rows, max_table, evaluate, first=None):
+        """The block walk of the exact local energies, once for every evaluator: rows [row_begin, row_begin + n_rows) of a
+        table of ``M`` in blocks of ``first`` rows (default: all of them at once); ``evaluate(b, n, capacity)`` produces rows
+        [b, b + n) with room for ``capacity`` connected states outside the table and returns (fitted, count).  A block whose
+        table + connected states would exceed ``max_table`` rows is halved and tried again; a single row that does not fit is
+        an error.  -> (connected states evaluated — a state reached from two blocks counting twice —, the block length
+        that last fitted)."""
+        from ._lib import NaqsError
+        ham = self.pauli_hamiltonian
+        room = int(max_table) - M
+        if room < 0 and n_rows > 0:
+            raise NaqsError(f"the table of {M} sampled states alone exceeds max_table = {int(max_table)}")
+        b, end, n_conn = row_begin, row_begin + n_rows, 0
+        step = n_rows if first is None else max(1, min(int(first), n_rows))
+        while b < end:
+            n = min(step, end - b)
+            fitted, count = evaluate(b, n, min(room, ham.connected_capacity(M, n)))
+            if not fitted:
+                if n == 1:
+                    raise NaqsError(f"row {b}: more than {room} connected states outside the table of {M} "
+                                    f"(at least {count}); max_table = {int(max_table)} cannot hold them")
+                step = (n + 1) // 2
+                continue
+            n_conn += count
+            b += n
+        return n_conn, step
+
+    @torch.no_grad()
+    def _exact_train_local_energy(self, fused, keys_buf, logpsi_buf, M, w):
+        """The training step's exact local energies of all M rows through ``naqs_exact_eloc``: the table sits in the first M
+        rows of the optimiser's key and log-psi buffers, every block appends its connected states behind it on the device.
+        The buffers grow on demand; the block length that last fitted is kept for the next step, so that a large table does
+        not probe an overflow every step (it is tried at twice that length again every 64th step, tables shrink too).
+        Per-block sums are added in block order.  -> (E_loc [M, 2], sums [4], connected states evaluated)."""
+        ham = self.pauli_hamiltonian
+        e_loc = torch.empty((M, 2), dtype=torch.float64, device=self.device)
+        sums = torch.empty(4, dtype=torch.float64, device=self.device)
+        part = None
+        bufs = [keys_buf, logpsi_buf]
+
+        def evaluate(b, n, capacity):
+            nonlocal part
+            if bufs[0].shape[0] < M + capacity:
+                bufs[0], bufs[1] = self._exact_buffers(M + capacity, keep=M)
+            first = b == 0
+            if not first and part is None:
+                part = torch.empty(4, dtype=torch.float64, device=self.device)
+            _, s, count, overflow = fused.exact_local_energy(ham, bufs[0], bufs[1], M, b, n, capacity, weights=w[b:b + n],
+                                                             out=e_loc[b:b + n], sums_out=sums if first else part)
+            if overflow:
+                return False, count
+            if not first:
+                sums.add_(s)
+            return True, count
+
+        first = self._exact_block_rows
+        if first is not None and first < M and self.n_steps % 64 == 63:
+            first = 2 * first
+        n_conn, step = self._walk_exact_blocks(M, 0, M, self.exact_max_table, evaluate, first=first)
+        self._exact_block_rows = None if step >= M else step
+        return e_loc, sums, n_conn
+
+    def _exact_buffers(self, rows, keep=0):
+        """The exact step's key and log-psi buffers with room for ``rows`` rows (the first ``keep`` rows survive a growth)."""
+        old = self._exact_bufs
+        if old is None or old[0].shape[0] < rows:
+            n = max(int(rows), 1024) if old is None else max(int(rows), 2 * old[0].shape[0])
+            n = max(int(rows), min(n, int(self.exact_max_table)))
+            new = (torch.empty(n, dtype=torch.int64, device=self.device), torch.empty((n, 2), dtype=torch.float32, device=self.device))
+            if old is not None and keep:
+                new[0][:keep].copy_(old[0][:keep])
+                new[1][:keep].copy_(old[1][:keep])
+            self._exact_bufs = new
+        return self._exact_bufs
+
     @torch.no_grad()
     def _exact_local_energy(self, keys, psi=None, log_psi=None, row_begin=0, n_rows=None, psi_fn=None, max_table=2 ** 22,
                             weights=None):
@@ -450,7 +537,6 @@ class OptimizerBase:
         table would exceed ``max_table`` rows is halved and tried again (an overflowing ``connected_keys`` call is a
         count, nothing more).  -> (E_loc float64 [n_rows, 2], weighted sums [4] of ``weights`` [n_rows] or None,
         number of states outside the table psi was evaluated on, a state reached from two blocks counting twice)."""
-        from ._lib import NaqsError
         if self.bug_compat_full_sample_order:
             raise NotImplementedError("exact local energies with bug_compat_full_sample_order: the quirk reorders the table")
         ham = self.pauli_hamiltonian
@@ -470,19 +556,12 @@ class OptimizerBase:
         sums = torch.zeros(4, dtype=torch.float64, device=self.device) if weights is not None else None
         if weights is not None:
             weights = weights.reshape(-1).to(self.device, torch.float64)
-        room = int(max_table) - M
-        if room < 0 and n_rows > 0:
-            raise NaqsError(f"the table of {M} sampled states alone exceeds max_table = {int(max_table)}")
-        b, end, step, n_conn = row_begin, row_begin + n_rows, n_rows, 0
-        while b < end:
-            n = min(step, end - b)
-            conn, count = ham.connected_keys(keys, b, n, capacity=min(room, ham.connected_capacity(M, n)))
+
+        def evaluate(b, n, capacity):
+            nonlocal sums
+            conn, count = ham.connected_keys(keys, b, n, capacity=capacity)
             if conn is None:
-                if n == 1:
-                    raise NaqsError(f"row {b}: more than {room} connected states outside the table of {M} "
-                                    f"(at least {count}); max_table = {int(max_table)} cannot hold them")
-                step = (n + 1) // 2
-                continue
+                return False, count
             if count:
                 lp_new = self._log_psi_of_keys(conn, psi_fn)
                 if kind == "psi":
@@ -497,8 +576,9 @@ class OptimizerBase:
                                          weights=weights[b - row_begin:b - row_begin + n])[1]
             else:
                 ham.local_energy(t_keys, t_wf, kind=kind, row_begin=b, n_rows=n, out=o)
-            n_conn += count
-            b += n
+            return True, count
+
+        n_conn, _ = self._walk_exact_blocks(M, row_begin, n_rows, max_table, evaluate)
         return out, sums, n_conn
 
     @torch.no_grad()
@@ -565,6 +645,9 @@ class OptimizerBase:
         # shard of rows this rank owns (the whole table when single-process)
         b, e_ = shard_bounds(M, rank, world)
         saved = None
+        exact, exact_bufs = self.exact_local_energies, None
+        if exact and dist is not None:           # (unreachable through _choose_dist_mode: exact mode never shards)
+            raise NotImplementedError("exact local energies in a row-sharded step")
         if log_psi is not None:
             # reference-style call: log psi of the whole table, carrying gradients
             lp_all, lp_mine = log_psi.reshape(-1, 2), log_psi.reshape(-1, 2)[b:e_]
@@ -574,7 +657,14 @@ class OptimizerBase:
             fused = self.wavefunction.fused(need_phase=True) if self.use_fused else None
             pre = None
             quirk = self._eloc_keys(keys) is not keys
-            if (fused is not None and regularisation_loss is None and not self.normalize_grads and world == 1
+            if (exact and fused is not None and regularisation_loss is None and not self.normalize_grads
+                    and fused.train_mode == "hip" and sample_weights is not None):
+                # exact local energies: the table's keys and log psi go to the front of the buffers that the library call
+                # below appends the connected states to
+                exact_bufs = self._exact_buffers(M)
+                exact_bufs[0][:M].copy_(keys)
+                lp_mine, saved = fused.forward_saved(exact_bufs[0][:M], out=exact_bufs[1][:M])
+            elif (fused is not None and regularisation_loss is None and not self.normalize_grads and world == 1 and not exact
                     and fused.train_mode == "hip" and sample_weights is not None and not quirk
                     and os.environ.get("NAQS_TRAIN_FUSED_ELOC", "1") == "1"):
                 # single GPU: forward (activations kept) + E_loc + weighted sums in one library call — or already done by
@@ -623,6 +713,15 @@ class OptimizerBase:
         # E_loc of the owned rows + (sum w Re, sum w Im, sum w Re^2, sum w) in one launch
         if log_psi is None and pre is not None:
             e_loc, sums = pre[2], pre[3]
+        elif exact:
+            # psi on every connected state: the library call on the optimiser's buffers, or — networks on the announced
+            # fallback, the BLAS phase mode, a caller's own log psi — the evaluation path's Python evaluator
+            if exact_bufs is not None:
+                e_loc, sums, n_conn = self._exact_train_local_energy(fused, exact_bufs[0], exact_bufs[1], M, w)
+            else:
+                e_loc, sums, n_conn = self._exact_local_energy(keys, log_psi=lp_all.detach(), max_table=self.exact_max_table,
+                                                               weights=w)
+            self._n_connected_pending += n_conn
         else:
             e_loc, sums = self.pauli_hamiltonian.local_energy(self._eloc_keys(keys), lp_all.detach(), kind="log_psi", row_begin=b,
                                                               n_rows=e_ - b, weights=w[b:e_])
@@ -765,9 +864,9 @@ class PartialSamplingOptimizer(OptimizerBase):
     """Optimise with partial sampling of the Hilbert space (energy.py:731-1056)."""
 
     def __init__(self, n_samples, n_samples_max=1e9, n_unq_samples_min=1000, n_unq_samples_max=1e6,
-                 log_exact_energy=True, **kwargs):
+                 log_exact_energy=True, exact_local_energies=False, **kwargs):
         kwargs['reweight_samples_by_psi'] = False
-        super().__init__(**kwargs)
+        super().__init__(exact_local_energies=exact_local_energies, **kwargs)
         self.log_exact_energy = log_exact_energy
         self.n_samples = int(n_samples)
         self.n_samples_max = int(n_samples_max)
@@ -825,8 +924,8 @@ class PartialSamplingOptimizer(OptimizerBase):
         """What the single-GPU fused branch of _SGD_step and every one-call form of the step (single process or sharded) have
         in common — everything except who owns the rows: the fused HIP path with nothing between forward and E_loc, and the
         A/B switches NAQS_TRAIN_FUSED_ELOC / NAQS_TRAIN_PREFUSE."""
-        if not self.use_fused or self.normalize_grads or self.bug_compat_full_sample_order:
-            return False
+        if not self.use_fused or self.normalize_grads or self.bug_compat_full_sample_order or self.exact_local_energies:
+            return False                     # (exact local energies: several library calls with the set's size learnt in between)
         if os.environ.get("NAQS_TRAIN_FUSED_ELOC", "1") != "1" or os.environ.get("NAQS_TRAIN_PREFUSE", "1") != "1":
             return False
         fused = self.wavefunction.fused(need_phase=True)
@@ -1182,6 +1281,9 @@ class PartialSamplingOptimizer(OptimizerBase):
                 var = self.log[LogKey.E_LOC_VAR][-1][1]
                 energy = self.calculate_energy(normalise_psi=True) if self.log_exact_energy else None
                 self.log[LogKey.E].append((self.n_steps, energy))
+                if self.exact_local_energies:       # connected states psi was evaluated on since the last output line
+                    self.n_connected.append((self.n_steps, self._n_connected_pending))
+                    self._n_connected_pending = 0
                 recent = [x[1] for x in self.log[LogKey.E_LOC][-min(output_freq, self.n_epochs):]]
                 tpe = (self.run_time - run_time_at_last_log) / output_freq
                 run_time_at_last_log = self.run_time
