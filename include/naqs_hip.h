@@ -426,6 +426,25 @@ int naqs_net_train_backward(naqs_net_t *net, int64_t M, const uint64_t *keys_dev
  * = loss.backward() of _SGD_step (src/optimizer/energy.py:328-343) given E_loc, the weights and the accumulators. */
 int naqs_net_train_backward_vmc(naqs_net_t *net, int64_t M, const uint64_t *keys_dev, const double *eloc_dev, const double *w_dev,
                                 const double *sums_dev, float *g_dev, double *ev_dev, float *grad_dev, void *stream);
+/* Natural-gradient training in sample space (minSR; no counterpart in the reference, whose two KFAC optimisers are unused).
+ * With log psi_i = a_i + i phi_i, A = d a / d theta, B = d phi / d theta, weights w (sum 1), D = diag(sqrt w) and the seeds
+ * g [M][2] of naqs_vmc_loss_grad:
+ *   X_a = D (A - 1 w^T A), T_a = X_a X_a^T, y_a = g[:, 0] / (2 sqrt w); X_phi, T_phi, y_phi likewise from B and g[:, 1];
+ *   d theta = X_a^T (T_a + lambda I)^-1 y_a + X_phi^T (T_phi + lambda I)^-1 y_phi, lambda = diag_shift * (mean diagonal of T).
+ * naqs_net_sr_gram writes T_a + lambda I and T_phi + lambda I ([M][M] float64, symmetric) and y_a, y_phi ([M] float64); the caller
+ * solves the two systems.  naqs_net_sr_direction forms the seeds s_i = sqrt(w_i) x_i - w_i sum_j sqrt(w_j) x_j per column and runs
+ * naqs_net_train_backward with them: dir_dev [naqs_net_param_count] float32 = d theta.  Both must follow naqs_net_train_forward of
+ * the SAME keys like naqs_net_train_backward.  The Gram matrices are built from per-layer float32 factors (no Jacobian) on the
+ * float64 matrix cores (exact products, float64 sums in a fixed order): deterministic.  Memory: the caller's two M x M matrices (16 M^2 bytes) plus
+ * O(M P Ha) floats of handle scratch; M > 32768 -> NAQS_ERR_UNSUPPORTED.  Single-phase and aggregate-phase handles with one hidden
+ * layer per block; combined blocks (W1 shared between a and phi) and deeper blocks -> NAQS_ERR_UNSUPPORTED.  diag_shift <= 0, M < 1
+ * or no training forward held -> NAQS_ERR_INVALID.  naqs_net_sr_gram_uncentred: G_a = A A^T and G_phi = B B^T as the kernels form
+ * them, before centring — for tests and measurements. */
+int naqs_net_sr_gram(naqs_net_t *net, int64_t M, const uint64_t *keys_dev, const double *w_dev, const float *g_dev, double diag_shift,
+                     double *Ta_dev, double *Tphi_dev, double *ya_dev, double *yphi_dev, void *stream);
+int naqs_net_sr_gram_uncentred(naqs_net_t *net, int64_t M, const uint64_t *keys_dev, double *Ga_dev, double *Gphi_dev, void *stream);
+int naqs_net_sr_direction(naqs_net_t *net, int64_t M, const uint64_t *keys_dev, const double *w_dev, const double *xa_dev,
+                          const double *xphi_dev, float *dir_dev, void *stream);
 /* naqs_net_train_forward and the local energies of the same table in one call (= naqs_logpsi_eloc that also keeps the
  * activations for naqs_net_train_backward): the single-GPU training step's forward half, three launches. */
 int naqs_net_train_forward_eloc(naqs_net_t *net, naqs_ham_t *ham, int64_t M, const uint64_t *keys_dev, const double *w_dev,

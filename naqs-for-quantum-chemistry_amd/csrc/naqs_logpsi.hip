@@ -2138,6 +2138,7 @@ NAQS_API int naqs_net_destroy(naqs_net_t *net) {
     if (net->d_scales) (void)hipFree(net->d_scales);
     if (net->d_ws_xchg) (void)hipFree(net->d_ws_xchg);
     if (net->d_sum_words) (void)hipFree(net->d_sum_words);
+    if (net->d_sr) (void)hipFree(net->d_sr);
     naqs::poll_handle_destroy(&net->poll);
     delete net;
     return NAQS_OK;

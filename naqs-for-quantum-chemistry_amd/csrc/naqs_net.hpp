@@ -383,6 +383,8 @@ struct naqs_net {
     bool hold_finish = false;               // in: the sampler leaves its finish job pending (fin_job) instead of launching it
     bool fin_pending = false;               // a finish job nobody has launched or hosted yet (naqs::net_sample_finish_flush)
     naqs::SampleFinishJob fin_job{};
+    void *d_sr = nullptr;                   // natural-gradient scratch (naqs_sr.hip): per-pair factors, unit seeds, seeds, row sums
+    int64_t sr_cap = 0;                     // rows it holds
 };
 
 namespace naqs {

@@ -31,6 +31,7 @@
 #include "naqs_amp_backward.hpp"
 #include "naqs_reduce.hpp"
 #include "naqs_pack.hpp"
+#include "naqs_sr.hpp"
 
 namespace {
 
@@ -1322,4 +1323,56 @@ NAQS_API int naqs_net_train_backward_vmc(naqs_net_t *net, int64_t M, const uint6
                                          const double *w_dev, const double *sums_dev, float *g_dev, double *ev_dev, float *grad_dev,
                                          void *stream) {
     return train_backward_vmc_impl(net, M, keys_dev, eloc_dev, w_dev, sums_dev, g_dev, ev_dev, grad_dev, stream, nullptr);
+}
+
+// ---- natural-gradient training (naqs_sr.hip): the phase MLP's per-sample factors, host sequencing only ----
+int naqs::net_sr_begin(naqs_net *net, int64_t M, hipStream_t s) {
+    const int stj = naqs::net_flush_pack(net, s);
+    if (stj != NAQS_OK) return stj;
+    if (!net->have_weights || !net->have_wb) return NAQS_ERR_INVALID;
+    if (naqs::has_phase_mlp(net) && (M > net->train_cap || !net->d_train)) return NAQS_ERR_INVALID;   // no training forward held
+    if (!naqs::has_phase_mlp(net) && (M > net->cap_M || !net->d_scratch)) return NAQS_ERR_INVALID;
+    return NAQS_OK;
+}
+
+// The deltas of every phase layer for the seeds unit_g = (., 1): d phase_i / d (layer l's output), left in the training
+// scratch where the unfused backward leaves them (leading dimension pad64(N_l)); the layer's input is the saved x or the
+// activation below.  Same kernels, same launch shapes as train_backward_impl's unfused chain.
+int naqs::net_sr_phase_factors(naqs_net *net, int64_t M, const uint64_t *keys_dev, const float *unit_g, naqs::SrJobs *jobs,
+                               hipStream_t s) {
+    if (!naqs::has_phase_mlp(net) || M <= 0 || M > net->train_cap || !net->d_train || !net->have_wb || !jobs) return NAQS_ERR_INVALID;
+    const NetDims &d = net->amp.d;
+    const TrainLayout L = train_layout(net, net->train_cap);
+    char *base = static_cast<char *>(net->d_train);
+    float *top = reinterpret_cast<float *>(base + L.top);
+    const float2 *g2 = reinterpret_cast<const float2 *>(unit_g);
+    const int H = d.n_lin - 1;
+    NAQS_KLAUNCH(top_delta_kernel, dim3((unsigned)((M * L.top_ld + 255) / 256)), dim3(256), 0, s, d, M, keys_dev, g2, top, L.top_ld);
+    HIP_TRY(hipGetLastError());
+    const float *dl[MAXL];
+    dl[H] = top;
+    for (int l = H; l > 0; --l) {
+        const int Np = pad64(net->phase_N[(size_t)l]), Kp = pad64(net->phase_K[(size_t)l]);
+        const float *in = reinterpret_cast<const float *>(base + L.act[l - 1]);
+        float *dnext = reinterpret_cast<float *>(base + L.delta[l - 1]);
+        if (l == H) {
+            NAQS_KLAUNCH(delta_below_top_kernel, dim3((unsigned)((M * (Kp >> 2) + 255) / 256)), dim3(256), 0, s, d, M, keys_dev, g2,
+                               net->d_wb + wb_offset(net, l), in, Kp, dnext);
+        } else {
+            NAQS_KLAUNCH(grad_in_kernel, dim3((unsigned)((M + TB - 1) / TB), Kp / TB), dim3(256), 0, s, dl[l],
+                               net->d_wb + wb_offset(net, l), in, M, Np, Kp, dnext);
+        }
+        HIP_TRY(hipGetLastError());
+        dl[l - 1] = dnext;
+    }
+    jobs->n = H + 1;
+    for (int l = 0; l <= H; ++l) {
+        const int N = net->phase_N[(size_t)l], K = net->phase_K[(size_t)l];
+        jobs->D[l] = dl[l]; jobs->ldd[l] = pad64(N); jobs->kd[l] = (N + 31) & ~31;
+        jobs->A[l] = l == 0 ? reinterpret_cast<const float *>(base + L.x) : reinterpret_cast<const float *>(base + L.act[l - 1]);
+        jobs->lda[l] = l == 0 ? L.x_ld : L.act_ld[l - 1];
+        jobs->ka[l] = (K + 31) & ~31;
+        jobs->one[l] = 1;
+    }
+    return NAQS_OK;
 }

@@ -1,0 +1,561 @@
+// naqs_sr.hip — natural-gradient training in sample space (minSR) for gfx950 (MI355X):
+//   naqs_net_sr_gram       keys, weights, loss seeds -> the two centred, shifted M x M Gram matrices T_a + lambda I,
+//                          T_phi + lambda I and the right-hand sides y_a, y_phi (all float64)
+//   naqs_net_sr_gram_uncentred  the two Gram matrices G_a, G_phi before centring (tests and measurements)
+//   naqs_net_sr_direction  the solutions x_a, x_phi -> the natural-gradient direction, through naqs_net_train_backward
+//
+// With log psi_i = a_i + i phi_i, A = d a / d theta, B = d phi / d theta (M x N_p), D = diag(sqrt w):
+//   X_a = D (A - 1 w^T A),  T_a = X_a X_a^T,  y_a = g[:, 0] / (2 sqrt w)   (likewise X_phi, T_phi, y_phi from B and g[:, 1])
+//   d theta = X_a^T (T_a + lambda I)^-1 y_a + X_phi^T (T_phi + lambda I)^-1 y_phi
+// The amplitude parameters move only a and the phase parameters only phi in the two supported families (single phase MLP,
+// per-pair phase blocks), so the two blocks decouple.  No Jacobian is formed: every parameter sits in a Linear layer, a
+// sample's gradient for it is delta_i (x) a_i, and the layer adds (Delta Delta^T) o (A A^T + 1) to the uncentred Gram matrix
+// G = A A^T — two thin GEMMs over the sample axis and one elementwise product per layer.
+//
+//   sr_amp_factors_kernel  stage (1) of amp_backward_pair (naqs_amp_backward.hpp) with unit seeds: per pair and sample the
+//                          block's inputs x (the bias as an explicit column of ones), hidden activations h, d-pre and d-out
+//   sr_gram_kernel         one workgroup per 64 x 64 tile (I, J >= I): per factor pair both products of the float32 factors on
+//                          v_mfma_f64_16x16x4_f64 (exact products, float64 sums), multiplied elementwise and accumulated in
+//                          float64 in a fixed order.  G is then EXACTLY the Gram matrix of the float32 factors: T is positive
+//                          semi-definite and T + lambda I factorises at any shift.  (On v_mfma_f32_16x16x4_f32 the two products
+//                          come back rounded to float32 — 1.8e-7 of sqrt(G_ii G_jj) from float64 instead of 1.1e-7, as noise
+//                          that is independent from element to element and that no Gram matrix has.)
+//   sr_rowsum_kernel       m = G w (fixed-order row sums), the diagonal, and the right-hand side
+//   sr_center_kernel       T = D (G - m 1^T - 1 m^T + c) D + lambda I in place, c = w^T G w, lambda = diag_shift * tr T / M
+//   sr_seeds_kernel        s_i = sqrt(w_i) x_i - w_i sum_j sqrt(w_j) x_j per column: X^T x = (backward pass with seeds s)
+// Every sum has a fixed order and there are no float atomics: the results are deterministic.
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+
+#include "naqs_common.hpp"
+#include "naqs_net.hpp"
+#include "naqs_amp_backward.hpp"
+#include "naqs_sr.hpp"
+
+namespace {
+
+using naqs::MAXP;
+using naqs::NetDims;
+using naqs::SrJobs;
+using naqs::WAVE;
+using naqs::DeviceGuard;
+using naqs::ampbw::GT;
+using naqs::ampbw::MAX_TILE_WGS;
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+
+constexpr int TB = 64;       // Gram tile edge
+constexpr int CH = 32;       // feature chunk staged in LDS
+constexpr int LDD = 34;      // row stride of a [64][CH] tile (naqs_phase_grad.hip: conflict-free for 16 rows x 2 k)
+constexpr int XLD = 64;      // leading dimension of the x and d-out factors; CH of their columns are written and read
+
+inline int pad64(int x) { return (x + 63) & ~63; }
+inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// where pair n's factors of one block set go: [pair][cap rows][ld]
+struct SrFactorOut { float *x, *dout, *h, *dh; int64_t cap; int ldh; };
+
+// One orbital pair NB, all tiles of this workgroup: amp_backward_pair's stage (1) — same forward, same d-out, same d-pre, wave
+// q owning hidden units 16 q .. 16 q + 15 — with the seed 1 for every valid sample, and the tile written out instead of
+// contracted.  smem as there: weights | d-pre tile [Ha][65] | h tile [Ha][65] | d-out [5][64] | input bits [64] | partial
+// outputs [Ha/16][5][64].  raw: the phase blocks of an aggregate-phase network.
+template <int NB>
+__device__ __forceinline__ void sr_factors_pair(const NetDims &d, const float *__restrict__ w, const int64_t M,
+                                                const uint64_t *__restrict__ keys, const SrFactorOut &F, float *smem, const int raw,
+                                                const int wg, const int n_wgs) {
+    constexpr int NIN = NB == 0 ? 1 : 2 * NB;
+    constexpr int S = naqs::amp_row_stride(NIN);
+    constexpr int LD = GT + 1;
+    static_assert(NIN + 1 <= CH, "the inputs and the bias fit one chunk of columns");
+    const int Ha = d.Ha, nout = d.n_out_amp, NW = Ha >> 4, NT = NW * WAVE;
+    const int w_floats = (Ha * S + 8 + 3) & ~3;
+    float *s_w = smem;
+    float *s_dpre = s_w + w_floats;
+    float *s_h = s_dpre + Ha * LD;
+    float *s_do = s_h + Ha * LD;                          // [5][GT]
+    uint32_t *s_x = reinterpret_cast<uint32_t *>(s_do + 5 * GT);
+    float *s_part = reinterpret_cast<float *>(s_x + GT);  // [NW][5][GT]
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    {
+        const f32x4 *from = reinterpret_cast<const f32x4 *>(w + d.amp_off[NB]);
+        f32x4 *to = reinterpret_cast<f32x4 *>(s_w);
+        for (int e = tid; e < (Ha * S + 8) / 4; e += NT) to[e] = from[e];
+    }
+    const float *b2 = s_w + Ha * S;
+    const int j0 = wave * 16;
+    float *xo = F.x + (int64_t)NB * F.cap * XLD, *doo = F.dout + (int64_t)NB * F.cap * XLD;
+    float *ho = F.h + (int64_t)NB * F.cap * F.ldh, *dho = F.dh + (int64_t)NB * F.cap * F.ldh;
+    __syncthreads();
+
+    for (int64_t t0 = (int64_t)wg * GT; t0 < M; t0 += (int64_t)n_wgs * GT) {
+        const int64_t i = t0 + lane;
+        const bool valid = i < M;
+        const uint64_t key = valid ? keys[i] : 0ull;
+        uint32_t abits = 0, bbits = 0;
+#pragma unroll
+        for (int k = 0; k < NB; ++k) {
+            abits |= (uint32_t)((key >> d.qa[k]) & 1ull) << k;
+            bbits |= (uint32_t)((key >> d.qb[k]) & 1ull) << k;
+        }
+        const int occ = (int)((key >> d.qa[NB]) & 1ull) + 2 * (int)((key >> d.qb[NB]) & 1ull);
+        const bool swap = (raw ? d.phase_sym != 0 : d.sym != 0) && abits > bbits;
+        const uint32_t first = swap ? bbits : abits, second = swap ? abits : bbits;
+        float x[NIN];
+        if (NB == 0) {
+            x[0] = 0.0f;
+        } else {
+#pragma unroll
+            for (int k = 0; k < NB; ++k) {
+                x[k] = ((first >> k) & 1u) ? 1.0f : -1.0f;
+                x[NB + k] = ((second >> k) & 1u) ? 1.0f : -1.0f;
+            }
+        }
+        const float gi = valid ? 1.0f : 0.0f;
+        float o[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll 2
+        for (int jj = j0; jj < j0 + 16; ++jj) {
+            float rv[S];
+            naqs::load_row<S>(s_w + jj * S, rv);
+            float h0 = rv[NIN], h1 = 0.0f;
+#pragma unroll
+            for (int k = 0; k + 1 < NIN; k += 2) { h0 = fmaf(rv[k], x[k], h0); h1 = fmaf(rv[k + 1], x[k + 1], h1); }
+            if (NIN & 1) h0 = fmaf(rv[NIN - 1], x[NIN - 1], h0);
+            const float h = fmaxf(h0 + h1, 0.0f);
+            s_h[jj * LD + lane] = h;
+#pragma unroll
+            for (int c = 0; c < 5; ++c)
+                if (c < nout) o[c] = fmaf(rv[NIN + 1 + c], h, o[c]);
+        }
+#pragma unroll
+        for (int c = 0; c < 5; ++c) s_part[(wave * 5 + c) * GT + lane] = o[c];
+        __syncthreads();
+#pragma unroll
+        for (int c = 0; c < 5; ++c) {
+            float v = c < nout ? b2[c] : 0.0f;
+            for (int q = 0; q < NW; ++q) v += s_part[(q * 5 + c) * GT + lane];
+            o[c] = v;
+        }
+        float da4[4];
+        if (raw) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) da4[c] = valid && c == naqs::phase_out_row(d, occ) ? gi : 0.0f;
+        } else {
+            float la[4];
+            bool ok[4];
+            naqs::amp_conditional<true>(d, NB, o, abits, bbits, la, ok);
+            const bool live = valid && (occ == 0 ? ok[0] : (occ == 1 ? ok[1] : (occ == 2 ? ok[2] : ok[3])));
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const float sm = ok[c] ? expf(2.0f * la[c]) : 0.0f;
+                da4[c] = live && ok[c] ? gi * ((c == occ ? 1.0f : 0.0f) - sm) : 0.0f;
+            }
+        }
+        float dout[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+        if (d.sym) {                                       // transpose of amp_symmetrise
+            const int x_order = abits > bbits ? 0 : (abits == bbits ? 1 : 2);
+            dout[0] = da4[0];
+            dout[2] = da4[3];
+            dout[1] = 0.5f * (da4[1] + da4[2]);
+            if (x_order == 1) dout[1] += 0.5f * (da4[1] + da4[2]);
+            else if (x_order == 0) { dout[3] = 0.5f * da4[1]; dout[4] = 0.5f * da4[2]; }
+            else { dout[4] = 0.5f * da4[1]; dout[3] = 0.5f * da4[2]; }
+        } else {
+            dout[0] = da4[0]; dout[1] = da4[1]; dout[2] = da4[2]; dout[3] = da4[3];
+        }
+        if (wave == 0) {
+#pragma unroll
+            for (int c = 0; c < 5; ++c) s_do[c * GT + lane] = dout[c];
+            s_x[lane] = (NB == 0 ? 0u : (first | (second << NB))) | (1u << NIN);   // bit NIN: the bias input
+        }
+#pragma unroll 4
+        for (int jj = j0; jj < j0 + 16; ++jj) {
+            const float *row = s_w + jj * S + NIN + 1;
+            float dh = 0.0f;
+#pragma unroll
+            for (int c = 0; c < 5; ++c)
+                if (c < nout) dh = fmaf(row[c], dout[c], dh);
+            s_dpre[jj * LD + lane] = s_h[jj * LD + lane] > 0.0f ? dh : 0.0f;
+        }
+        __syncthreads();
+        // the tile's factors, row-major: consecutive threads take consecutive columns of a sample's row
+        for (int e = tid; e < GT * Ha; e += NT) {
+            const int r = e / Ha, j = e - r * Ha;
+            if (t0 + r < M) {
+                ho[(t0 + r) * F.ldh + j] = s_h[j * LD + r];
+                dho[(t0 + r) * F.ldh + j] = s_dpre[j * LD + r];
+            }
+        }
+        for (int e = tid; e < GT * CH; e += NT) {
+            const int r = e / CH, c = e - r * CH;
+            if (t0 + r < M) {
+                const uint32_t xb = s_x[r];
+                float xv = 0.0f;
+                if (c < NIN) xv = NB == 0 ? 0.0f : (((xb >> c) & 1u) ? 1.0f : -1.0f);      // (pair 0: the constant-zero input)
+                else if (c == NIN) xv = 1.0f;
+                xo[(t0 + r) * XLD + c] = xv;
+                doo[(t0 + r) * XLD + c] = c < 5 ? s_do[c * GT + r] : 0.0f;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// amp_backward_kernel's launch shape: workgroup = pair blockIdx.y x a strided set of 64-sample tiles, Ha / 16 waves
+__global__ __launch_bounds__(512) void sr_amp_factors_kernel(const NetDims d, const float *__restrict__ w, const int64_t M,
+                                                             const uint64_t *__restrict__ keys, const SrFactorOut F, const int raw) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int wg = (int)blockIdx.x, n_wgs = (int)gridDim.x;
+    switch ((int)blockIdx.y) {
+#define NAQS_CASE(NB) case NB: sr_factors_pair<NB>(d, w, M, keys, F, smem, raw, wg, n_wgs); break;
+        NAQS_CASE(0) NAQS_CASE(1) NAQS_CASE(2) NAQS_CASE(3) NAQS_CASE(4) NAQS_CASE(5) NAQS_CASE(6) NAQS_CASE(7)
+        NAQS_CASE(8) NAQS_CASE(9) NAQS_CASE(10) NAQS_CASE(11) NAQS_CASE(12) NAQS_CASE(13) NAQS_CASE(14) NAQS_CASE(15)
+#undef NAQS_CASE
+        default: break;
+    }
+}
+
+// acc[a][b] += F[I rows][0..K) . F[J rows][0..K)^T for this wave's 32 x 32 sub-block (2 x 2 MFMA tiles): 32-deep chunks of both
+// row tiles staged in LDS as [64][CH] (rows >= M read as zero), the next chunk fetched while this one's MFMAs run.
+// A operand: lane (m, q) holds Is[row m][k = q]; B operand: Js[row m][k = q], both widened to float64 (exact); the float64 form's
+// D: col = lane & 15 (J), row = (lane >> 4) + 4 r (I) — not the float32 forms' map.
+__device__ __forceinline__ void sr_tile_product(const float *__restrict__ Fm, const int ld, const int K, const int64_t M,
+                                                const int64_t i0, const int64_t j0, float *Is, float *Js, f64x4 (&acc)[2][2]) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wi = wave >> 1, wj = wave & 1, lm = lane & 15, lq = lane >> 4;
+    f32x4 vi[2], vj[2];
+    auto fetch = [&](int k0) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int e = tid + 256 * u, r = e >> 3, c4 = e & 7;
+            vi[u] = (f32x4){0.f, 0.f, 0.f, 0.f}; vj[u] = vi[u];
+            if (i0 + r < M) vi[u] = *reinterpret_cast<const f32x4 *>(Fm + (i0 + r) * ld + k0 + 4 * c4);
+            if (j0 + r < M) vj[u] = *reinterpret_cast<const f32x4 *>(Fm + (j0 + r) * ld + k0 + 4 * c4);
+        }
+    };
+    fetch(0);
+    for (int k0 = 0; k0 < K; k0 += CH) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int e = tid + 256 * u, r = e >> 3, c4 = e & 7;
+            float2 *di = reinterpret_cast<float2 *>(Is + r * LDD + 4 * c4);       // LDD even: 8-byte aligned
+            float2 *dj = reinterpret_cast<float2 *>(Js + r * LDD + 4 * c4);
+            di[0] = make_float2(vi[u][0], vi[u][1]); di[1] = make_float2(vi[u][2], vi[u][3]);
+            dj[0] = make_float2(vj[u][0], vj[u][1]); dj[1] = make_float2(vj[u][2], vj[u][3]);
+        }
+        __syncthreads();
+        if (k0 + CH < K) fetch(k0 + CH);
+#pragma unroll
+        for (int ks = 0; ks < CH / 4; ++ks) {
+            const int kk = ks * 4 + lq;
+            const double a0 = Is[(wi * 32 + lm) * LDD + kk], a1 = Is[(wi * 32 + 16 + lm) * LDD + kk];
+            const double b0 = Js[(wj * 32 + lm) * LDD + kk], b1 = Js[(wj * 32 + 16 + lm) * LDD + kk];
+            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+}
+
+// G[I, J] = sum_l (D_l D_l^T)[I, J] o ((A_l A_l^T)[I, J] + one_l), l in the jobs' order, for the tile (I = blockIdx.x,
+// J = blockIdx.y >= I) and its transpose.  The whole feature axis of a factor is one workgroup's: no split, no second pass.
+__global__ __launch_bounds__(256) void sr_gram_kernel(const SrJobs J, const int64_t M, double *__restrict__ G) {
+    if (blockIdx.y < blockIdx.x) return;
+    __shared__ __attribute__((aligned(16))) float Is[TB * LDD];
+    __shared__ __attribute__((aligned(16))) float Js[TB * LDD];
+    const int64_t i0 = (int64_t)blockIdx.x * TB, j0 = (int64_t)blockIdx.y * TB;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wi = wave >> 1, wj = wave & 1, lm = lane & 15, lq = lane >> 4;
+    double g[2][2][4];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) g[a][b][r] = 0.0;
+    for (int l = 0; l < J.n; ++l) {
+        f64x4 pd[2][2], pa[2][2];
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) { pd[a][b] = (f64x4){0.0, 0.0, 0.0, 0.0}; pa[a][b] = pd[a][b]; }
+        sr_tile_product(J.D[l], J.ldd[l], J.kd[l], M, i0, j0, Is, Js, pd);
+        sr_tile_product(J.A[l], J.lda[l], J.ka[l], M, i0, j0, Is, Js, pa);
+        const double one = J.one[l] ? 1.0 : 0.0;
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) g[a][b][r] += pd[a][b][r] * (pa[a][b][r] + one);
+    }
+    const bool off_diag = blockIdx.y != blockIdx.x;
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int64_t i = i0 + wi * 32 + a * 16 + lq + 4 * r, j = j0 + wj * 32 + b * 16 + lm;
+                if (i < M && j < M) {
+                    G[i * M + j] = g[a][b][r];
+                    if (off_diag) G[j * M + i] = g[a][b][r];
+                }
+            }
+}
+
+// sum over the 256 threads of a workgroup in a fixed order (butterfly within a wave, the four waves added in order): every
+// thread gets the same bits.  s_red: 4 doubles of LDS; ends with a barrier so that s_red can be used again.
+__device__ __forceinline__ double block_sum_256(double v, double *s_red) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const double t = ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
+    __syncthreads();
+    return t;
+}
+
+// one wave per row i: m_i = sum_j G_ij w_j (lane-strided partial sums in ascending j, then the butterfly), the diagonal
+// element, and the right-hand side y_i = g[i][col] / (2 sqrt w_i)
+__global__ __launch_bounds__(256) void sr_rowsum_kernel(const int64_t M, const double *__restrict__ G, const double *__restrict__ w,
+                                                        const float *__restrict__ g, const int col, double *__restrict__ m,
+                                                        double *__restrict__ diag, double *__restrict__ y) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= M) return;
+    const double *row = G + i * M;
+    double v = 0.0;
+    for (int64_t j = lane; j < M; j += 64) v += row[j] * w[j];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    if (lane == 0) {
+        m[i] = v;
+        diag[i] = row[i];
+        y[i] = (double)g[2 * i + col] / (2.0 * sqrt(w[i]));
+    }
+}
+
+// T = D (G - m 1^T - 1 m^T + c) D + lambda I in place, 16 rows per workgroup.  c = w^T G w = sum_i w_i m_i and the trace
+// tr T = sum_i w_i (G_ii - 2 m_i + c) are formed by every workgroup itself from m, the saved diagonal and w, in the same
+// fixed order: the same bits everywhere, and no launch or hand-over in between.
+constexpr int CENTER_ROWS = 16;
+__global__ __launch_bounds__(256) void sr_center_kernel(const int64_t M, double *__restrict__ G, const double *__restrict__ w,
+                                                        const double *__restrict__ m, const double *__restrict__ diag,
+                                                        const double diag_shift) {
+    __shared__ double s_red[4];
+    double s_wm = 0.0, s_wd = 0.0, s_w = 0.0;
+    for (int64_t i = threadIdx.x; i < M; i += 256) {
+        const double wi = w[i];
+        s_wm += wi * m[i];
+        s_wd += wi * diag[i];
+        s_w += wi;
+    }
+    const double c = block_sum_256(s_wm, s_red);
+    const double wd = block_sum_256(s_wd, s_red), ws = block_sum_256(s_w, s_red);
+    const double lambda = diag_shift * (((wd - 2.0 * c) + c * ws) / (double)M);
+    const int64_t r0 = (int64_t)blockIdx.x * CENTER_ROWS;
+    for (int r = 0; r < CENTER_ROWS; ++r) {
+        const int64_t i = r0 + r;
+        if (i >= M) break;
+        const double mi = m[i], si = sqrt(w[i]);
+        double *row = G + i * M;
+        for (int64_t j = threadIdx.x; j < M; j += 256) {
+            const double t = si * (((row[j] - mi) - m[j]) + c) * sqrt(w[j]);
+            row[j] = i == j ? t + lambda : t;
+        }
+    }
+}
+
+// s[i][col] = sqrt(w_i) x_i - w_i sum_j sqrt(w_j) x_j for both columns (x_a, x_phi), as float32 seeds for the backward pass;
+// every workgroup forms the two sums itself, in the same fixed order
+__global__ __launch_bounds__(256) void sr_seeds_kernel(const int64_t M, const double *__restrict__ w, const double *__restrict__ xa,
+                                                       const double *__restrict__ xp, float2 *__restrict__ s) {
+    __shared__ double s_red[4];
+    double pa = 0.0, pp = 0.0;
+    for (int64_t j = threadIdx.x; j < M; j += 256) {
+        const double sq = sqrt(w[j]);
+        pa += sq * xa[j];
+        pp += sq * xp[j];
+    }
+    const double Sa = block_sum_256(pa, s_red), Sp = block_sum_256(pp, s_red);
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= M) return;
+    const double wi = w[i], sq = sqrt(wi);
+    s[i] = make_float2((float)(sq * xa[i] - wi * Sa), (float)(sq * xp[i] - wi * Sp));
+}
+
+// carve-up of net->d_sr for `cap` rows
+struct SrLayout {
+    size_t x[2], dout[2], h[2], dh[2];      // per block set: [P][cap][ld] floats
+    size_t unit, seeds;                     // [cap][2] floats: the constant seeds (1, 1), the direction's seeds
+    size_t m[2], diag[2];                   // [cap] doubles per Gram block
+    int ldh[2];
+    size_t total;
+};
+
+SrLayout sr_layout(const naqs_net *net, const int64_t cap) {
+    SrLayout L{};
+    size_t off = 0;
+    const int n_sets = naqs::has_second_set(net) ? 2 : 1;
+    for (int k = 0; k < n_sets; ++k) {
+        const NetDims &d = k == 0 ? net->amp.d : net->ph.d;
+        L.ldh[k] = pad64(d.Ha);
+        const size_t thin = (size_t)d.P * cap * XLD * sizeof(float), wide = (size_t)d.P * cap * L.ldh[k] * sizeof(float);
+        L.x[k] = off; off = up256(off + thin);
+        L.dout[k] = off; off = up256(off + thin);
+        L.h[k] = off; off = up256(off + wide);
+        L.dh[k] = off; off = up256(off + wide);
+    }
+    L.unit = off; off = up256(off + (size_t)cap * 2 * sizeof(float));
+    L.seeds = off; off = up256(off + (size_t)cap * 2 * sizeof(float));
+    for (int k = 0; k < 2; ++k) {
+        L.m[k] = off; off = up256(off + (size_t)cap * sizeof(double));
+        L.diag[k] = off; off = up256(off + (size_t)cap * sizeof(double));
+    }
+    L.total = off;
+    return L;
+}
+
+int ensure_sr_scratch(naqs_net *net, const int64_t M) {
+    if (M <= net->sr_cap && net->d_sr) return NAQS_OK;
+    HIP_TRY(hipDeviceSynchronize());
+    if (net->d_sr) (void)hipFree(net->d_sr);
+    net->d_sr = nullptr; net->sr_cap = 0;
+    const int64_t cap = std::min<int64_t>(naqs::SR_MAX_ROWS, std::max<int64_t>(1024, M + M / 4));
+    const SrLayout L = sr_layout(net, cap);
+    if (hipMalloc(&net->d_sr, L.total) != hipSuccess) { net->d_sr = nullptr; return NAQS_ERR_NOMEM; }
+    HIP_TRY(hipMemset(net->d_sr, 0, L.total));             // the factors' padding columns stay zero for good
+    HIP_TRY(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(static_cast<char *>(net->d_sr) + L.unit), 0x3f800000, (size_t)cap * 2));
+    HIP_TRY(hipDeviceSynchronize());
+    net->sr_cap = cap;
+    return NAQS_OK;
+}
+
+// the per-pair factors of one block set and its jobs: pair n adds (d-out, h | +1) then (d-pre, x with the bias column)
+int sr_block_factors(naqs_net *net, const naqs::BlockSet &set, const int k, const SrLayout &L, const int64_t M,
+                     const uint64_t *keys_dev, SrJobs *jobs, hipStream_t s) {
+    const NetDims &d = set.d;
+    if (d.Ha > 128 || (d.Ha & 15) || set.deep() || 2 * d.P > naqs::SR_MAX_JOBS) return NAQS_ERR_UNSUPPORTED;
+    const size_t lds = naqs::ampbw::smem_floats(d) * sizeof(float);
+    if (lds > 156 * 1024) return NAQS_ERR_UNSUPPORTED;
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&sr_amp_factors_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
+    char *base = static_cast<char *>(net->d_sr);
+    SrFactorOut F;
+    F.x = reinterpret_cast<float *>(base + L.x[k]); F.dout = reinterpret_cast<float *>(base + L.dout[k]);
+    F.h = reinterpret_cast<float *>(base + L.h[k]); F.dh = reinterpret_cast<float *>(base + L.dh[k]);
+    F.cap = net->sr_cap; F.ldh = L.ldh[k];
+    const int n_wg = (int)std::min<int64_t>(MAX_TILE_WGS, (M + GT - 1) / GT);
+    NAQS_KLAUNCH(sr_amp_factors_kernel, dim3((unsigned)n_wg, (unsigned)d.P), dim3((unsigned)((d.Ha >> 4) * WAVE)), lds, s, d, set.w, M,
+                       keys_dev, F, set.raw ? 1 : 0);
+    HIP_TRY(hipGetLastError());
+    jobs->n = 2 * d.P;
+    const int kh = (d.Ha + 31) & ~31;
+    for (int n = 0; n < d.P; ++n) {
+        const int64_t thin = (int64_t)n * F.cap * XLD, wide = (int64_t)n * F.cap * F.ldh;
+        jobs->D[2 * n] = F.dout + thin; jobs->ldd[2 * n] = XLD; jobs->kd[2 * n] = CH;
+        jobs->A[2 * n] = F.h + wide; jobs->lda[2 * n] = F.ldh; jobs->ka[2 * n] = kh; jobs->one[2 * n] = 1;
+        jobs->D[2 * n + 1] = F.dh + wide; jobs->ldd[2 * n + 1] = F.ldh; jobs->kd[2 * n + 1] = kh;
+        jobs->A[2 * n + 1] = F.x + thin; jobs->lda[2 * n + 1] = XLD; jobs->ka[2 * n + 1] = CH; jobs->one[2 * n + 1] = 0;
+    }
+    return NAQS_OK;
+}
+
+// what both entry points refuse
+int sr_supported(const naqs_net *net) {
+    if (net->family == naqs::Family::COMBINED) return NAQS_ERR_UNSUPPORTED;       // W1 of the last block is shared between a and phi
+    if (net->amp.deep() || net->ph.deep()) return NAQS_ERR_UNSUPPORTED;           // more than one hidden layer per block
+    return NAQS_OK;
+}
+
+}  // namespace
+
+// the factors and the two uncentred Gram matrices G_a -> T[0], G_phi -> T[1]
+static int sr_gram_impl(naqs_net_t *net, int64_t M, const uint64_t *keys_dev, double *const T[2], hipStream_t s) {
+    int st = naqs::net_sr_begin(net, M, s);
+    if (st != NAQS_OK) return st;
+    st = ensure_sr_scratch(net, M);
+    if (st != NAQS_OK) return st;
+    const SrLayout L = sr_layout(net, net->sr_cap);
+    char *base = static_cast<char *>(net->d_sr);
+    SrJobs ja{}, jp{};
+    st = sr_block_factors(net, net->amp, 0, L, M, keys_dev, &ja, s);
+    if (st != NAQS_OK) return st;
+    if (naqs::has_phase_mlp(net)) st = naqs::net_sr_phase_factors(net, M, keys_dev, reinterpret_cast<const float *>(base + L.unit), &jp, s);
+    else st = sr_block_factors(net, net->ph, 1, L, M, keys_dev, &jp, s);
+    if (st != NAQS_OK) return st;
+    const unsigned nt = (unsigned)((M + TB - 1) / TB);
+    NAQS_KLAUNCH(sr_gram_kernel, dim3(nt, nt), dim3(256), 0, s, ja, M, T[0]);
+    HIP_TRY(hipGetLastError());
+    NAQS_KLAUNCH(sr_gram_kernel, dim3(nt, nt), dim3(256), 0, s, jp, M, T[1]);
+    HIP_TRY(hipGetLastError());
+    return NAQS_OK;
+}
+
+NAQS_API int naqs_net_sr_gram_uncentred(naqs_net_t *net, int64_t M, const uint64_t *keys_dev, double *Ga_dev, double *Gphi_dev,
+                                        void *stream) {
+    if (!net) return NAQS_ERR_INVALID;
+    int st = sr_supported(net);
+    if (st != NAQS_OK) return st;
+    if (M < 1 || !keys_dev || !Ga_dev || !Gphi_dev) return NAQS_ERR_INVALID;
+    if (M > naqs::SR_MAX_ROWS) return NAQS_ERR_UNSUPPORTED;
+    DeviceGuard guard;
+    st = guard.init(net->device);
+    if (st != NAQS_OK) return st;
+    double *const T[2] = {Ga_dev, Gphi_dev};
+    return sr_gram_impl(net, M, keys_dev, T, reinterpret_cast<hipStream_t>(stream));
+}
+
+NAQS_API int naqs_net_sr_gram(naqs_net_t *net, int64_t M, const uint64_t *keys_dev, const double *w_dev, const float *g_dev,
+                              double diag_shift, double *Ta_dev, double *Tphi_dev, double *ya_dev, double *yphi_dev, void *stream) {
+    if (!net) return NAQS_ERR_INVALID;
+    int st = sr_supported(net);
+    if (st != NAQS_OK) return st;
+    if (M < 1 || !(diag_shift > 0.0) || !keys_dev || !w_dev || !g_dev || !Ta_dev || !Tphi_dev || !ya_dev || !yphi_dev) return NAQS_ERR_INVALID;
+    if (M > naqs::SR_MAX_ROWS) return NAQS_ERR_UNSUPPORTED;
+    DeviceGuard guard;
+    st = guard.init(net->device);
+    if (st != NAQS_OK) return st;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    double *const T[2] = {Ta_dev, Tphi_dev};
+    double *const y[2] = {ya_dev, yphi_dev};
+    st = sr_gram_impl(net, M, keys_dev, T, s);
+    if (st != NAQS_OK) return st;
+    const SrLayout L = sr_layout(net, net->sr_cap);
+    char *base = static_cast<char *>(net->d_sr);
+    for (int k = 0; k < 2; ++k) {
+        double *m = reinterpret_cast<double *>(base + L.m[k]), *diag = reinterpret_cast<double *>(base + L.diag[k]);
+        NAQS_KLAUNCH(sr_rowsum_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, M, T[k], w_dev, g_dev, k, m, diag, y[k]);
+        HIP_TRY(hipGetLastError());
+        NAQS_KLAUNCH(sr_center_kernel, dim3((unsigned)((M + CENTER_ROWS - 1) / CENTER_ROWS)), dim3(256), 0, s, M, T[k], w_dev, m, diag,
+                           diag_shift);
+        HIP_TRY(hipGetLastError());
+    }
+    return NAQS_OK;
+}
+
+NAQS_API int naqs_net_sr_direction(naqs_net_t *net, int64_t M, const uint64_t *keys_dev, const double *w_dev, const double *xa_dev,
+                                   const double *xphi_dev, float *dir_dev, void *stream) {
+    if (!net) return NAQS_ERR_INVALID;
+    int st = sr_supported(net);
+    if (st != NAQS_OK) return st;
+    if (M < 1 || !keys_dev || !w_dev || !xa_dev || !xphi_dev || !dir_dev) return NAQS_ERR_INVALID;
+    if (M > naqs::SR_MAX_ROWS) return NAQS_ERR_UNSUPPORTED;
+    DeviceGuard guard;
+    st = guard.init(net->device);
+    if (st != NAQS_OK) return st;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    st = naqs::net_sr_begin(net, M, s);
+    if (st != NAQS_OK) return st;
+    st = ensure_sr_scratch(net, M);
+    if (st != NAQS_OK) return st;
+    const SrLayout L = sr_layout(net, net->sr_cap);
+    float *seeds = reinterpret_cast<float *>(static_cast<char *>(net->d_sr) + L.seeds);
+    NAQS_KLAUNCH(sr_seeds_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, M, w_dev, xa_dev, xphi_dev,
+                       reinterpret_cast<float2 *>(seeds));
+    HIP_TRY(hipGetLastError());
+    return naqs_net_train_backward(net, M, keys_dev, seeds, dir_dev, stream);
+}

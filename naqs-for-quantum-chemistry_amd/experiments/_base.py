@@ -51,6 +51,8 @@ _VALUE_FLAGS = [
     (("-save_freq",), "save_freq", dict(type=int, help="The saving frequency (in epochs).")),
     (("-n_excitations_max",), "n_excitations_max", dict(type=int, help="Maximum number of excitations.")),
     (("-s", "--seed"), "seed", dict(type=int, help="Training seed.")),
+    (("-sr_shift",), "sr_shift", dict(type=float, help="Natural gradient: diagonal shift, relative to the mean diagonal.")),
+    (("-sr_lr",), "sr_lr", dict(type=float, help="Natural gradient: learning rate.")),
 ]
 # (flags, dest, default expression on the get_parser keywords, help)
 _SWITCHES = [
@@ -72,6 +74,7 @@ _SWITCHES = [
      "After training, estimate the energy from a fresh sample with exact local energies (psi on every connected state)."),
     (("-train_exact_eloc",), "train_exact_eloc", lambda k: k["train_exact_eloc"],
      "Train on exact local energies (psi on every connected state)"),
+    (("-sr",), "sr", lambda k: k["sr"], "Train with the natural gradient (stochastic reconfiguration in sample space, minSR)."),
 ]
 _DEFAULTS = dict(molecule="molecules/H2", hamiltonian_fname=None, out=None, number=1, qubit_ordering=-1, lr=-1,
                  lr_lut=1e-2, n_samps=1e6, n_samps_max=1e12, n_unq_samps_min=50000, n_unq_samps_max=1e5,
@@ -80,7 +83,8 @@ _DEFAULTS = dict(molecule="molecules/H2", hamiltonian_fname=None, out=None, numb
                  load_hamiltonian=False, overwrite_hamiltonian=False, presolve_hamiltonian=False,
                  pretrained_model_loc=None, cont=False, n_excitations_max=-1, comb_amp_phase=False,
                  use_amp_spin_sym=True, use_phase_spin_sym=False, aggregate_phase=True, restrict_H=True,
-                 reset_opt=False, verbose=False, seed=-1, exact_eloc=False, train_exact_eloc=False)
+                 reset_opt=False, verbose=False, seed=-1, exact_eloc=False, train_exact_eloc=False,
+                 sr=False, sr_shift=1e-3, sr_lr=0.1)
 
 
 def get_parser(**overrides):
@@ -178,7 +182,11 @@ def _run(molecule_fname, hamiltonian_fname, exp_name, num_experiments, pretraine
          reweight_samples_by_psi, n_train, n_pretrain, output_freq, save_freq, n_lut, n_hid, n_layer, n_hid_phase,
          n_layer_phase, n_excitations_max, comb_amp_phase, use_amp_spin_sym, use_phase_spin_sym, aggregate_phase,
          use_restrictedH, loadH, presolveH, overwrite_pauli_hamiltonian, verbose, seed, device=None, exact_eloc=False,
-         train_exact_eloc=False):
+         train_exact_eloc=False, sr=False, sr_shift=1e-3, sr_lr=0.1):
+    if sr and (comb_amp_phase or n_layer != 1 or n_lut):
+        raise NotImplementedError("-sr (natural gradient): single-phase and aggregate-phase networks with one hidden layer per block "
+                                  "only; -comb_amp_phase shares the last block's first layer between amplitude and phase, and "
+                                  "-n_layer > 1 is not built")
     # (-phase_sym runs on the HIP kernels since round 5, -comb_amp_phase with -single_phase and -n_layer 1 too (naqs_net_create_combined;
     # with the aggregate phase or deeper blocks as PyTorch modules on the device) — no published script uses either; -n_pretrain is
     # OptimizerBase.pre_flatten; -weight_by_psi is accepted and, as in the reference, has no effect on this optimiser:
@@ -197,7 +205,8 @@ def _run(molecule_fname, hamiltonian_fname, exp_name, num_experiments, pretraine
                            continue_experiment, reset_optimizer, qubit_ordering, masking, lr, lr_lut, n_samps, n_samps_max,
                            n_unq_samps_min, n_unq_samps_max, n_train, n_pretrain, output_freq, save_freq, n_lut, n_hid, n_layer,
                            n_hid_phase, n_layer_phase, comb_amp_phase, use_amp_spin_sym, use_phase_spin_sym, aggregate_phase,
-                           use_restrictedH, presolveH, verbose, seed, device, exact_eloc, train_exact_eloc)
+                           use_restrictedH, presolveH, verbose, seed, device, exact_eloc, train_exact_eloc,
+                           dict(diag_shift=sr_shift, lr=sr_lr) if sr else None)
     finally:
         if locked[0]:
             _SETUP_LOCK.release()
@@ -210,7 +219,7 @@ def _run_locked(locked, molecule_fname, hamiltonian_fname, exp_name, num_experim
                 reset_optimizer, qubit_ordering, masking, lr, lr_lut, n_samps, n_samps_max, n_unq_samps_min, n_unq_samps_max,
                 n_train, n_pretrain, output_freq, save_freq, n_lut, n_hid, n_layer, n_hid_phase, n_layer_phase, comb_amp_phase,
                 use_amp_spin_sym, use_phase_spin_sym, aggregate_phase, use_restrictedH, presolveH, verbose, seed, device,
-                exact_eloc=False, train_exact_eloc=False):
+                exact_eloc=False, train_exact_eloc=False, natural_gradient=None):
     seed = set_global_seed(_agree_on_seed(seed))
     molecule, qubit_hamiltonian = load_molecule(molecule_fname, hamiltonian_fname=hamiltonian_fname, verbose=True)
     N = molecule.n_qubits
@@ -263,7 +272,7 @@ def _run_locked(locked, molecule_fname, hamiltonian_fname, exp_name, num_experim
             optimizer_args=[{'lr': lr, 'betas': (0.9, 0.99), 'weight_decay': 0, 'eps': 1e-15, 'amsgrad': False},
                             {'lr': lr_lut}],
             save_loc=exp_name_i, pauli_hamiltonian_dtype=np.float64, verbose=verbose, seed=seed + i,
-            exact_local_energies=train_exact_eloc)
+            exact_local_energies=train_exact_eloc, **({"natural_gradient": natural_gradient} if natural_gradient else {}))
         print("\n---System summary---\n")
         print(f"Size of restricted subspace : {hilbert.size}.")
         print("Qubit ordering in model :", wavefunction.qubit2model_permutation)
@@ -458,7 +467,9 @@ def _run_job(args, molecule_fname, seed):
     masking = NadeMasking.NONE if args.no_mask_psi else (NadeMasking.FULL if args.full_mask_psi else NadeMasking.PARTIAL)
     print(f"Running experimental script: {__file__}\nResults will be saved to: {exp_name}/\n\nscript options:")
     for key, val in sorted(vars(args).items()):
-        if key in ("exact_eloc", "train_exact_eloc") and not val:      # an opt-in of this port: without it the listing is the reference's
+        if key in ("exact_eloc", "train_exact_eloc", "sr") and not val:      # an opt-in of this port: without it the listing is the reference's
+            continue
+        if key in ("sr_shift", "sr_lr") and not args.sr:
             continue
         print(f"\t{key} : {val}")
     print("")
@@ -475,7 +486,7 @@ def _run_job(args, molecule_fname, seed):
                 use_phase_spin_sym=args.phase_sym, aggregate_phase=not args.single_phase,
                 use_restrictedH=not args.no_restrictedH, loadH=args.loadH, presolveH=args.presolveH,
                 overwrite_pauli_hamiltonian=args.overwriteH, verbose=args.verbose, seed=seed, exact_eloc=args.exact_eloc,
-                train_exact_eloc=args.train_exact_eloc)
+                train_exact_eloc=args.train_exact_eloc, **(dict(sr=True, sr_shift=args.sr_shift, sr_lr=args.sr_lr) if args.sr else {}))
 
 
 def run(*args, **kwargs):

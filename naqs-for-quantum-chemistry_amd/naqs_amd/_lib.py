@@ -83,6 +83,9 @@ SIGNATURES = {
     "naqs_vmc_sample_forward_eloc": (ctypes.c_int, [c_vp, c_vp, c_i64, ctypes.c_uint64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                                     c_vp, ctypes.POINTER(c_i64), c_vp]),
     "naqs_net_train_backward": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "naqs_net_sr_gram": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "naqs_net_sr_gram_uncentred": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "naqs_net_sr_direction": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "naqs_adam_step": (ctypes.c_int, [c_i64, c_vp, c_vp, c_vp, c_vp, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                       ctypes.c_double, ctypes.c_double, c_i64, c_vp]),
     "naqs_net_phase_inputs": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),

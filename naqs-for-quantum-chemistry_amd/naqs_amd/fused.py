@@ -331,6 +331,56 @@ class FusedLogPsi:
             if l > 0:
                 delta = (delta @ lin[l].weight).mul_(acts[l] > 0)
 
+    # ---- natural gradient in sample space (minSR): naqs_net_sr_gram / naqs_net_sr_direction ----------------
+    def _sr_check(self):
+        if self.comb or self.amp_depth != 1:
+            raise NotImplementedError("natural gradient (minSR): single-phase and aggregate-phase networks with one hidden layer per "
+                                      "block only (combined blocks share W1 between amplitude and phase; deeper blocks are not built)")
+
+    @torch.no_grad()
+    def sr_gram(self, saved, weights, g, diag_shift, uncentred=False):
+        """The two M x M systems of the natural-gradient step for the table of ``forward_saved`` (HIP mode; ``saved`` its token):
+        -> (T_a + lambda I, T_phi + lambda I, y_a, y_phi), float64 on the device, T = D (G - m 1^T - 1 m^T + c) D with G the Gram
+        matrix of the per-sample gradients of log|psi| (phase), D = diag(sqrt w), m = G w, c = w^T G w, lambda = ``diag_shift``
+        x the mean diagonal of T, y = g[:, k] / (2 sqrt w).  ``uncentred``: -> (G_a, G_phi) alone (tests, measurements).
+        Memory: 16 M^2 bytes for the two matrices; M <= 32768."""
+        self._sr_check()
+        keys = saved[0]
+        if saved[1] is not None:
+            raise NotImplementedError("sr_gram needs the token of forward_saved in HIP mode")
+        M = keys.shape[0]
+        Ta = torch.empty((M, M), dtype=torch.float64, device=self.device)
+        Tp = torch.empty((M, M), dtype=torch.float64, device=self.device)
+        if uncentred:
+            st = self._lib.naqs_net_sr_gram_uncentred(self._h, M, keys.data_ptr(), Ta.data_ptr(), Tp.data_ptr(), _stream_ptr(self.device))
+            _lib.check(st, "naqs_net_sr_gram_uncentred")
+            return Ta, Tp
+        w = weights.to(device=self.device, dtype=torch.float64).contiguous()
+        g = g.to(device=self.device, dtype=torch.float32).contiguous()
+        ya = torch.empty(M, dtype=torch.float64, device=self.device)
+        yp = torch.empty(M, dtype=torch.float64, device=self.device)
+        st = self._lib.naqs_net_sr_gram(self._h, M, keys.data_ptr(), w.data_ptr(), g.data_ptr(), float(diag_shift), Ta.data_ptr(),
+                                        Tp.data_ptr(), ya.data_ptr(), yp.data_ptr(), _stream_ptr(self.device))
+        _lib.check(st, "naqs_net_sr_gram")
+        return Ta, Tp, ya, yp
+
+    @torch.no_grad()
+    def sr_direction(self, saved, weights, xa, xphi, out=None):
+        """d theta = X_a^T x_a + X_phi^T x_phi as a flat float32 vector in state_dict order (``naqs_net_sr_direction``): the
+        seeds s_i = sqrt(w_i) x_i - w_i sum_j sqrt(w_j) x_j per column, then the training backward with them."""
+        self._sr_check()
+        keys = saved[0]
+        M = keys.shape[0]
+        w = weights.to(device=self.device, dtype=torch.float64).contiguous()
+        xa = xa.to(device=self.device, dtype=torch.float64).contiguous()
+        xphi = xphi.to(device=self.device, dtype=torch.float64).contiguous()
+        if out is None:
+            out = torch.empty(self.n_params, dtype=torch.float32, device=self.device)
+        st = self._lib.naqs_net_sr_direction(self._h, M, keys.data_ptr(), w.data_ptr(), xa.data_ptr(), xphi.data_ptr(), out.data_ptr(),
+                                             _stream_ptr(self.device))
+        _lib.check(st, "naqs_net_sr_direction")
+        return out
+
     def log_psi(self, keys, out=None):
         """keys: int64 device tensor [M] (uint64 bit patterns, qubit order) -> float32 [M, 2]."""
         M = keys.shape[0]

@@ -99,6 +99,10 @@ def _freeze_garbage_collector():
     _GC_FROZEN = True
 
 
+class NaturalGradientError(RuntimeError):
+    """The Cholesky factorisation of a shifted Gram matrix of the natural-gradient step failed (not positive definite)."""
+
+
 class OptimizerBase:
     def __init__(self, wavefunction, qubit_hamiltonian, pre_compute_H=True, n_electrons=None,
                  n_alpha_electrons=None, n_beta_electrons=None, n_fixed_electrons=None, n_excitations_max=None,
@@ -288,8 +292,8 @@ class OptimizerBase:
             elif self._dist_mode == "sharded" and mode != "sharded":
                 self._check_shards()
             m = self.wavefunction.model
-            if self.exact_local_energies:
-                mode = "replicated"          # exact local energies: no sharded step at any table size
+            if self.exact_local_energies or getattr(self, "natural_gradient", None):
+                mode = "replicated"          # exact local energies / natural gradient: no sharded step at any table size
             elif getattr(m, "combined_amp_phase_blocks", False) and not m.aggregate_phase:
                 mode = "replicated"          # -single_phase -comb_amp_phase: no sharded step (naqs_vmc_shard_* refuse its handles)
             elif m.aggregate_phase and len(m.amp_layers[0].linears()) > 2:
@@ -748,7 +752,17 @@ class OptimizerBase:
             self._shard_mismatch = (~shard_ok if self._shard_mismatch is None else self._shard_mismatch | ~shard_ok)
         self.optimizer.zero_grad()
         ev = None
-        if saved is not None:
+        natural = getattr(self, "natural_gradient", None)
+        if natural and (saved is None or saved[1] is not None or world != 1):
+            raise NotImplementedError("natural gradient: the step needs the HIP training forward of the whole table (a fused network in "
+                                      "HIP mode, sampled weights, no regularisation loss, no normalize_grads, no caller's log psi)")
+        if natural:
+            # minSR: the loss seeds as below, the two M x M systems from the Gram kernels, two float64 Cholesky solves on the
+            # device, the direction as a backward pass with the solutions as seeds, and theta -= lr * direction (no Adam)
+            g, ev = fused.vmc_loss_grad(e_loc, w.contiguous(), sums, with_energy=True)
+            self._natural_gradient_update(fused, saved, w.contiguous(), g)
+            self._loss_terms, self._last_loss = (g, lp_mine), None
+        elif saved is not None:
             # d loss / d log psi of vmc_loss, written out: (2 w Re(E_loc - <E>), -2 w Im(E_loc - <E>)); the same launch
             # leaves (<E>, Var) of energy.py:372-375 on the device
             g, ev = fused.backward_from_local_energy(saved, e_loc, w[b:e_].contiguous(), sums)
@@ -774,8 +788,9 @@ class OptimizerBase:
                 for p in params:
                     p.grad.copy_(flat[off:off + p.numel()].view_as(p))
                     off += p.numel()
-        self._clip_grads()
-        self.optimizer.step()
+        if not natural:
+            self._clip_grads()
+            self.optimizer.step()
         self.wavefunction.parameters_changed()
         if self.use_fused and saved is not None and os.environ.get("NAQS_TRAIN_EARLY_REFRESH", "1") == "1":
             # re-pack the kernels' weight layouts NOW, behind the optimiser launch, instead of at the start of the next
@@ -796,6 +811,23 @@ class OptimizerBase:
         self._check_shards()
         energy, variance = ev.tolist()
         return float(energy), float(variance)
+
+    def _natural_gradient_update(self, fused, saved, w, g):
+        """theta -= lr * [X_a^T (T_a + lambda I)^-1 y_a + X_phi^T (T_phi + lambda I)^-1 y_phi] (``FusedLogPsi.sr_gram`` /
+        ``sr_direction``); the two solves are torch's Cholesky in float64 on the device.  A factorisation that reports failure
+        raises ``NaturalGradientError``; nothing is retried."""
+        ng = self.natural_gradient
+        Ta, Tp, ya, yp = fused.sr_gram(saved, w, g, ng["diag_shift"])
+        xs = []
+        for name, T, y in (("amplitude", Ta, ya), ("phase", Tp, yp)):
+            L, info = torch.linalg.cholesky_ex(T)
+            if int(info.item()) != 0:
+                raise NaturalGradientError(f"natural gradient: Cholesky of the {name} block ({T.shape[0]} x {T.shape[0]}, "
+                                           f"diag_shift {ng['diag_shift']:g}) failed at leading minor {int(info.item())}")
+            xs.append(torch.cholesky_solve(y.unsqueeze(1), L).squeeze(1))
+        direction = fused.sr_direction(saved, w, xs[0], xs[1])
+        self.wavefunction.flatten_parameters().add_(direction, alpha=-float(ng["lr"]))
+        self.sr_last = dict(M=int(T.shape[0]), direction_norm=direction.norm())
 
     # ---- checkpoints / logs: same keys as the reference (energy.py:400-538) ----
     def _fmt(self, fname):
@@ -864,7 +896,14 @@ class PartialSamplingOptimizer(OptimizerBase):
     """Optimise with partial sampling of the Hilbert space (energy.py:731-1056)."""
 
     def __init__(self, n_samples, n_samples_max=1e9, n_unq_samples_min=1000, n_unq_samples_max=1e6,
-                 log_exact_energy=True, exact_local_energies=False, **kwargs):
+                 log_exact_energy=True, exact_local_energies=False, natural_gradient=None, **kwargs):
+        # natural_gradient: None (Adam, as always) or dict(diag_shift=..., lr=...): stochastic reconfiguration in sample space
+        # (minSR) on the Gram kernels of naqs_sr.hip; the optimiser passed in optimizer= is then never stepped
+        if natural_gradient is not None:
+            natural_gradient = dict(natural_gradient)
+            if set(natural_gradient) != {"diag_shift", "lr"} or not natural_gradient["diag_shift"] > 0 or not natural_gradient["lr"] > 0:
+                raise ValueError("natural_gradient: dict(diag_shift > 0, lr > 0)")
+        self.natural_gradient = natural_gradient
         kwargs['reweight_samples_by_psi'] = False
         super().__init__(exact_local_energies=exact_local_energies, **kwargs)
         self.log_exact_energy = log_exact_energy
@@ -926,6 +965,8 @@ class PartialSamplingOptimizer(OptimizerBase):
         A/B switches NAQS_TRAIN_FUSED_ELOC / NAQS_TRAIN_PREFUSE."""
         if not self.use_fused or self.normalize_grads or self.bug_compat_full_sample_order or self.exact_local_energies:
             return False                     # (exact local energies: several library calls with the set's size learnt in between)
+        if getattr(self, "natural_gradient", None):
+            return False                     # (natural gradient: the two solves sit between the library calls; _SGD_step runs it)
         if os.environ.get("NAQS_TRAIN_FUSED_ELOC", "1") != "1" or os.environ.get("NAQS_TRAIN_PREFUSE", "1") != "1":
             return False
         fused = self.wavefunction.fused(need_phase=True)

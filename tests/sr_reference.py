@@ -1,0 +1,152 @@
+"""The float64 reference of the natural-gradient step (a plain helper module, like grad_reference.py).
+
+Definitions (include/naqs_hip.h, naqs_net_sr_gram): log psi_i = a_i + i phi_i, A = d a / d theta, B = d phi / d theta
+(M x N_p, columns in state_dict order), weights w (sum 1), D = diag(sqrt w), seeds g [M, 2]:
+
+    X_a = D (A - 1 w^T A),   T_a = X_a X_a^T,   y_a = g[:, 0] / (2 sqrt w)          (X_phi, T_phi, y_phi from B, g[:, 1])
+    lambda = diag_shift * mean(diag T)                                              (per block)
+    d theta = X_a^T (T_a + lambda I)^-1 y_a + X_phi^T (T_phi + lambda I)^-1 y_phi
+
+* ``CASES`` / ``make_net`` / ``table``   the networks and key tables tests/test_sr_gpu.py runs, one sector each;
+* ``jacobians``                          A, B row by row through torch.autograd.grad on a CPU copy of the network (float64: the
+                                         reference; float32: the yardstick, its rows taken to float64 before any product);
+* ``gram_err``                           max_ij |G - G64|_ij / sqrt(G64_ii G64_jj);
+* ``system`` / ``direction``             the definitions above in float64 numpy (dense solve);
+* ``direction_f32``                      the same step as a float32 network on the CPU takes it: the direction's yardstick.
+"""
+import numpy as np
+import torch
+
+import grad_reference as gr
+
+TAU = 1e-5          # kink margin (float64 pre-activation) below which a row is left out, as in the backward tests
+
+# (sector, aggregate, amp_hidden, phase_hidden, amp_sym, masking).  Not the full product of the axes — each value of every axis
+# (family x amplitude width x phase shape x symmetry x masking) meets each sector at least once where the sector allows it, and
+# each pair of values of two axes meets somewhere:  H2 (P = 2: pair 0's constant input is half the network), syn10_3_2 (P = 5: one
+# level behind the sampler's head), LiH (P = 6), syn32_8_8 (P = 16: the ABI's largest, bit 31 of the keys in use).
+CASES = [
+    ("H2", False, 16, (32,), True, "PARTIAL"),
+    ("H2", True, 16, (32,), False, "FULL"),
+    ("syn10_3_2", False, 64, (64, 64), True, "FULL"),
+    ("syn10_3_2", True, 64, (32,), True, "PARTIAL"),
+    ("LiH", False, 16, (32,), False, "PARTIAL"),
+    ("LiH", False, 64, (64, 64), True, "PARTIAL"),
+    ("LiH", True, 16, (32,), True, "FULL"),
+    ("syn32_8_8", False, 64, (32,), True, "PARTIAL"),
+    ("syn32_8_8", False, 16, (64, 64), False, "FULL"),
+    ("syn32_8_8", True, 64, (32,), False, "PARTIAL"),
+]
+ROWS = (1, 63, 64, 65, 200)     # the tile edge, padded rows, I = J and I < J tiles; capped by the sector's size (H2: 4, syn10_3_2: 100)
+
+
+def case_id(case):
+    name, agg, ha, ph, sym, mask = case
+    return f"{name}-{'agg' if agg else 'single'}-a{ha}-p{'x'.join(map(str, ph))}-{'sym' if sym else 'nosym'}-{mask}"
+
+
+def make_net(case, device="cuda", seed=3):
+    """(hilbert, network) of a case, default-initialised from ``seed`` (the parameters are drawn on the CPU: the same on any device)."""
+    from naqs_amd.hilbert import Encoding, Hilbert
+    from naqs_amd.nade import NadeMasking
+    from naqs_amd.wavefunction import NAQSComplex_NADE_orbitals
+    name, agg, ha, ph, sym, mask = case
+    _, N, na, nb, _ = gr.sector(name)
+    hil = Hilbert.get(N, na, nb, encoding=Encoding.SIGNED)
+    torch.manual_seed(seed)
+    wf = NAQSComplex_NADE_orbitals(hil, device=device, qubit_ordering=-1, masking=NadeMasking[mask], amp_hidden_size=[ha],
+                                   phase_hidden_size=list(ph), use_amp_spin_sym=sym, use_phase_spin_sym=False, aggregate_phase=agg,
+                                   n_alpha_electrons=na, n_beta_electrons=nb)
+    return hil, wf
+
+
+def states_of(hil, keys):
+    return hil.idx2state(torch.as_tensor(np.asarray(keys).astype(np.int64)))
+
+
+def table(hil, w64, rows=max(ROWS), seed=5):
+    """Up to ``rows`` distinct keys of the sector in ascending order, none within TAU of a ReLU kink of the float64 network, and
+    random positive weights (sum 1 over the whole table; a leading part is renormalised by its user)."""
+    cand = np.sort(gr.random_keys(hil, min(hil.size, rows + rows // 4), seed=seed))
+    _, margin = gr.log_psi_and_kink_margin(w64, states_of(hil, cand))
+    keys = cand[margin >= TAU][:rows]
+    rs = np.random.RandomState(seed + 1)
+    w = rs.random_sample(len(keys)) + 0.1
+    return keys, w / w.sum()
+
+
+def jacobians(wf, states):
+    """(A, B) float64 numpy [M, N_p]: rows d log|psi_i| / d theta and d phase_i / d theta of the CPU network ``wf`` in its own
+    dtype, one torch.autograd.grad per row and component, columns in state_dict order."""
+    params = list(wf.model.parameters())
+    lp = wf.log_psi(states).reshape(-1, 2)
+    M = lp.shape[0]
+    out = np.zeros((2, M, sum(p.numel() for p in params)))
+    for i in range(M):
+        for c in range(2):
+            gs = torch.autograd.grad(lp[i, c], params, retain_graph=True, allow_unused=True)
+            out[c, i] = torch.cat([(torch.zeros_like(p) if g is None else g).reshape(-1) for p, g in zip(params, gs)]).double().numpy()
+    return out[0], out[1]
+
+
+def gram_err(G, G64):
+    d = np.sqrt(np.diag(G64))
+    scale = np.outer(d, d)
+    return float(np.max(np.abs(np.asarray(G, np.float64) - G64) / np.where(scale > 0, scale, 1.0)))
+
+
+def system(J, w, g_col, diag_shift):
+    """One block: (T + lambda I, y, X) float64 from the Jacobian J [M, N_p], weights w [M] and a column of the seeds."""
+    sw = np.sqrt(w)
+    X = sw[:, None] * (J - (w @ J)[None, :])
+    T = X @ X.T
+    lam = diag_shift * np.trace(T) / len(w)
+    return T + lam * np.eye(len(w)), np.asarray(g_col, np.float64) / (2 * sw), X
+
+
+def centred(G, w, diag_shift):
+    """T + lambda I from an uncentred Gram matrix: D (G - m 1^T - 1 m^T + c) D, m = G w, c = w^T G w."""
+    sw = np.sqrt(w)
+    m = G @ w
+    T = sw[:, None] * (G - m[:, None] - m[None, :] + w @ m) * sw[None, :]
+    return T + diag_shift * np.trace(T) / len(w) * np.eye(len(w))
+
+
+def direction(A, B, w, g, diag_shift):
+    """d theta float64 [N_p] by dense solves."""
+    out = 0.0
+    for J, col in ((A, 0), (B, 1)):
+        T, y, X = system(J, w, np.asarray(g)[:, col], diag_shift)
+        out = out + X.T @ np.linalg.solve(T, y)
+    return out
+
+
+def direction_f32(w32, states, A32, B32, w, g, diag_shift):
+    """The float32-CPU pipeline, the yardstick of the kernels' direction: float32 Jacobian rows of the float32 network ``w32``, the
+    two systems and their solves in float64, the seeds s_i = sqrt(w_i) x_i - w_i sum_j sqrt(w_j) x_j rounded to float32, and
+    X^T x as the float32 autograd backward of sum_i s_i . log psi_i — what ``naqs_net_sr_direction`` does with its kernels."""
+    sw = np.sqrt(w)
+    seeds = []
+    for J, col in ((A32, 0), (B32, 1)):
+        T, y, _ = system(J, w, np.asarray(g)[:, col], diag_shift)
+        x = np.linalg.solve(T, y)
+        seeds.append(sw * x - w * (sw @ x))
+    grads = gr.grad_f64(w32, states, np.stack(seeds, -1).astype(np.float32))
+    return np.concatenate([grads[n].reshape(-1) for n, _ in w32.model.named_parameters()])
+
+
+def per_tensor_err(wf, got, want):
+    """max over the parameter tensors of max |got - want| / max |want| on the tensor's slice of the flat vectors (the backward
+    tests' measure; a tensor whose reference slice is zero — pair 0's first-layer weights see a constant-zero input — must be zero)."""
+    worst, off = 0.0, 0
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    for name, p in wf.model.named_parameters():
+        n = p.numel()
+        a, b = got[off:off + n], want[off:off + n]
+        off += n
+        scale = np.abs(b).max()
+        if scale == 0:
+            assert np.all(a == 0), name
+            continue
+        worst = max(worst, float(np.abs(a - b).max() / scale))
+    return worst
