@@ -431,8 +431,8 @@ int naqs_net_train_backward_vmc(naqs_net_t *net, int64_t M, const uint64_t *keys
  * g [M][2] of naqs_vmc_loss_grad:
  *   X_a = D (A - 1 w^T A), T_a = X_a X_a^T, y_a = g[:, 0] / (2 sqrt w); X_phi, T_phi, y_phi likewise from B and g[:, 1];
  *   d theta = X_a^T (T_a + lambda I)^-1 y_a + X_phi^T (T_phi + lambda I)^-1 y_phi, lambda = diag_shift * (mean diagonal of T).
- * naqs_net_sr_gram writes T_a + lambda I and T_phi + lambda I ([M][M] float64, symmetric) and y_a, y_phi ([M] float64); the caller
- * solves the two systems.  naqs_net_sr_direction forms the seeds s_i = sqrt(w_i) x_i - w_i sum_j sqrt(w_j) x_j per column and runs
+ * naqs_net_sr_gram writes T_a + lambda I and T_phi + lambda I ([M][M] float64, symmetric) and y_a, y_phi ([M] float64);
+ * naqs_net_sr_solve (below) or the caller's own library solves the two systems.  naqs_net_sr_direction forms the seeds s_i = sqrt(w_i) x_i - w_i sum_j sqrt(w_j) x_j per column and runs
  * naqs_net_train_backward with them: dir_dev [naqs_net_param_count] float32 = d theta.  Both must follow naqs_net_train_forward of
  * the SAME keys like naqs_net_train_backward.  The Gram matrices are built from per-layer float32 factors (no Jacobian) on the
  * float64 matrix cores (exact products, float64 sums in a fixed order): deterministic.  Memory: the caller's two M x M matrices (16 M^2 bytes) plus
@@ -445,6 +445,21 @@ int naqs_net_sr_gram(naqs_net_t *net, int64_t M, const uint64_t *keys_dev, const
 int naqs_net_sr_gram_uncentred(naqs_net_t *net, int64_t M, const uint64_t *keys_dev, double *Ga_dev, double *Gphi_dev, void *stream);
 int naqs_net_sr_direction(naqs_net_t *net, int64_t M, const uint64_t *keys_dev, const double *w_dev, const double *xa_dev,
                           const double *xphi_dev, float *dir_dev, void *stream);
+/* The solves between naqs_net_sr_gram and naqs_net_sr_direction: T x = y for the one or two symmetric positive definite [M][M]
+ * row-major float64 matrices that naqs_net_sr_gram wrote, by a blocked Cholesky factorisation T = L L^T (64-wide block columns,
+ * the trailing updates on the float64 matrix cores) and the forward and back substitutions, all in float64 — what
+ * torch.linalg.cholesky_ex / torch.cholesky_solve do in the optimiser (naqs_amd/optimizer.py:833-837).  Asynchronous on
+ * `stream`; both systems travel in the same 3 ceil(M / 64) launches.  Tphi_dev, yphi_dev and xphi_dev may be NULL together: one
+ * system.  T is OVERWRITTEN: on return its lower triangle with the diagonal holds L, the strict upper triangle is unspecified.
+ * x must not alias y or T; y is not written.  info_dev [2] int32, one word per system (both are written), LAPACK's potrf
+ * convention: 0 = factorised, otherwise p + 1 for the first pivot p (0-based) with !(pivot > 0), so a NaN pivot fails too.  A
+ * failed system's x is NaN throughout and its T is unspecified; the other system is unaffected bit for bit.  Deterministic: the
+ * same bits on repetition, and for a system solved alone or beside another, in either slot.  `net` supplies the device and
+ * 0.6 MB of scratch of its own (one solve at a time per handle): any family of handle, no training forward needed.
+ * Null net, M < 1, a null required pointer or a partly null phi triple -> NAQS_ERR_INVALID; M > 32768 -> NAQS_ERR_UNSUPPORTED
+ * (checked before any buffer is touched). */
+int naqs_net_sr_solve(naqs_net_t *net, int64_t M, double *Ta_dev, double *Tphi_dev, const double *ya_dev, const double *yphi_dev,
+                      double *xa_dev, double *xphi_dev, int32_t *info_dev, void *stream);
 /* naqs_net_train_forward and the local energies of the same table in one call (= naqs_logpsi_eloc that also keeps the
  * activations for naqs_net_train_backward): the single-GPU training step's forward half, three launches. */
 int naqs_net_train_forward_eloc(naqs_net_t *net, naqs_ham_t *ham, int64_t M, const uint64_t *keys_dev, const double *w_dev,

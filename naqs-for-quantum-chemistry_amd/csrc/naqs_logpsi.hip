@@ -2139,6 +2139,7 @@ NAQS_API int naqs_net_destroy(naqs_net_t *net) {
     if (net->d_ws_xchg) (void)hipFree(net->d_ws_xchg);
     if (net->d_sum_words) (void)hipFree(net->d_sum_words);
     if (net->d_sr) (void)hipFree(net->d_sr);
+    if (net->d_sr_solve) (void)hipFree(net->d_sr_solve);
     naqs::poll_handle_destroy(&net->poll);
     delete net;
     return NAQS_OK;

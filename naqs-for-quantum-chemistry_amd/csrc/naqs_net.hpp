@@ -385,6 +385,7 @@ struct naqs_net {
     naqs::SampleFinishJob fin_job{};
     void *d_sr = nullptr;                   // natural-gradient scratch (naqs_sr.hip): per-pair factors, unit seeds, seeds, row sums
     int64_t sr_cap = 0;                     // rows it holds
+    void *d_sr_solve = nullptr;             // naqs_net_sr_solve's scratch (naqs_sr_solve.hip): next diagonal block and z, per system
 };
 
 namespace naqs {

@@ -381,6 +381,30 @@ class FusedLogPsi:
         _lib.check(st, "naqs_net_sr_direction")
         return out
 
+    @torch.no_grad()
+    def sr_solve(self, Ta, Tp, ya, yp):
+        """T x = y for the systems of ``sr_gram`` by the library's blocked float64 Cholesky (``naqs_net_sr_solve``) -> (x_a, x_phi,
+        info).  ``Ta`` and ``Tp`` are OVERWRITTEN: on return their lower triangles (with the diagonal) hold the factors L, the
+        strict upper triangles are unspecified.  ``info``: int32 device tensor [2], LAPACK's potrf convention per system (0, or
+        p + 1 for the first pivot p that is not positive); a failed system's x is NaN throughout.  ``Tp = yp = None``: one system,
+        x_phi is None.  Any network family; no training forward is needed.  One solve at a time per network (handle scratch)."""
+        two = Tp is not None
+        if two != (yp is not None):
+            raise ValueError("sr_solve: Tp and yp come together or not at all")
+        M = Ta.shape[0]
+        for T, y in ((Ta, ya), (Tp, yp))[:2 if two else 1]:
+            if T.dtype != torch.float64 or y.dtype != torch.float64 or not T.is_contiguous() or not y.is_contiguous() \
+                    or T.shape != (M, M) or y.shape != (M,) or T.device != self.device or y.device != self.device:
+                raise ValueError("sr_solve: contiguous float64 [M, M] matrices and [M] right-hand sides on the network's device")
+        xa = torch.empty(M, dtype=torch.float64, device=self.device)
+        xp = torch.empty(M, dtype=torch.float64, device=self.device) if two else None
+        info = torch.empty(2, dtype=torch.int32, device=self.device)
+        st = self._lib.naqs_net_sr_solve(self._h, M, Ta.data_ptr(), Tp.data_ptr() if two else None, ya.data_ptr(),
+                                         yp.data_ptr() if two else None, xa.data_ptr(), xp.data_ptr() if two else None,
+                                         info.data_ptr(), _stream_ptr(self.device))
+        _lib.check(st, "naqs_net_sr_solve")
+        return xa, xp, info
+
     def log_psi(self, keys, out=None):
         """keys: int64 device tensor [M] (uint64 bit patterns, qubit order) -> float32 [M, 2]."""
         M = keys.shape[0]

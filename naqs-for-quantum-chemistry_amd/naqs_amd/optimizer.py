@@ -814,10 +814,20 @@ class OptimizerBase:
 
     def _natural_gradient_update(self, fused, saved, w, g):
         """theta -= lr * [X_a^T (T_a + lambda I)^-1 y_a + X_phi^T (T_phi + lambda I)^-1 y_phi] (``FusedLogPsi.sr_gram`` /
-        ``sr_direction``); the two solves are torch's Cholesky in float64 on the device.  A factorisation that reports failure
-        raises ``NaturalGradientError``; nothing is retried."""
+        ``sr_direction``); the two solves are torch's Cholesky in float64 on the device, or with ``solver="hip"`` the library's
+        (``FusedLogPsi.sr_solve``).  A factorisation that reports failure raises ``NaturalGradientError``; nothing is retried."""
         ng = self.natural_gradient
         Ta, Tp, ya, yp = fused.sr_gram(saved, w, g, ng["diag_shift"])
+        if ng.get("solver", "torch") == "hip":
+            xa, xp, info = fused.sr_solve(Ta, Tp, ya, yp)
+            for name, minor in zip(("amplitude", "phase"), info.tolist()):
+                if minor != 0:
+                    raise NaturalGradientError(f"natural gradient: Cholesky of the {name} block ({Ta.shape[0]} x {Ta.shape[0]}, "
+                                               f"diag_shift {ng['diag_shift']:g}) failed at leading minor {minor}")
+            direction = fused.sr_direction(saved, w, xa, xp)
+            self.wavefunction.flatten_parameters().add_(direction, alpha=-float(ng["lr"]))
+            self.sr_last = dict(M=int(Ta.shape[0]), direction_norm=direction.norm(), solver="hip")
+            return
         xs = []
         for name, T, y in (("amplitude", Ta, ya), ("phase", Tp, yp)):
             L, info = torch.linalg.cholesky_ex(T)
@@ -827,7 +837,7 @@ class OptimizerBase:
             xs.append(torch.cholesky_solve(y.unsqueeze(1), L).squeeze(1))
         direction = fused.sr_direction(saved, w, xs[0], xs[1])
         self.wavefunction.flatten_parameters().add_(direction, alpha=-float(ng["lr"]))
-        self.sr_last = dict(M=int(T.shape[0]), direction_norm=direction.norm())
+        self.sr_last = dict(M=int(T.shape[0]), direction_norm=direction.norm(), solver="torch")
 
     # ---- checkpoints / logs: same keys as the reference (energy.py:400-538) ----
     def _fmt(self, fname):
@@ -897,12 +907,14 @@ class PartialSamplingOptimizer(OptimizerBase):
 
     def __init__(self, n_samples, n_samples_max=1e9, n_unq_samples_min=1000, n_unq_samples_max=1e6,
                  log_exact_energy=True, exact_local_energies=False, natural_gradient=None, **kwargs):
-        # natural_gradient: None (Adam, as always) or dict(diag_shift=..., lr=...): stochastic reconfiguration in sample space
-        # (minSR) on the Gram kernels of naqs_sr.hip; the optimiser passed in optimizer= is then never stepped
+        # natural_gradient: None (Adam, as always) or dict(diag_shift=..., lr=...[, solver="torch" | "hip"]): stochastic
+        # reconfiguration in sample space (minSR) on the Gram kernels of naqs_sr.hip; the optimiser passed in optimizer= is then
+        # never stepped.  solver: who solves the two systems — torch's Cholesky (the default) or naqs_net_sr_solve
         if natural_gradient is not None:
             natural_gradient = dict(natural_gradient)
-            if set(natural_gradient) != {"diag_shift", "lr"} or not natural_gradient["diag_shift"] > 0 or not natural_gradient["lr"] > 0:
-                raise ValueError("natural_gradient: dict(diag_shift > 0, lr > 0)")
+            if set(natural_gradient) - {"solver"} != {"diag_shift", "lr"} or natural_gradient.get("solver", "torch") not in ("torch", "hip") \
+                    or not natural_gradient["diag_shift"] > 0 or not natural_gradient["lr"] > 0:
+                raise ValueError('natural_gradient: dict(diag_shift > 0, lr > 0[, solver="torch" | "hip"])')
         self.natural_gradient = natural_gradient
         kwargs['reweight_samples_by_psi'] = False
         super().__init__(exact_local_energies=exact_local_energies, **kwargs)

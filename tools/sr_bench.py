@@ -3,9 +3,12 @@ steps / wall time to an energy with the natural gradient and with Adam from the 
 
     python tools/sr_bench.py [--rows 1500,10000] [--reps 20]                  the calls of one step (HIP events around each call)
     python tools/sr_bench.py --converge LiH --target -7.8810 --max-steps 500  steps and seconds until <E> of a step <= target
+                             [--sr-solver hip]                                with the library's Cholesky solve
 
 The calls: the training forward; naqs_net_sr_gram_uncentred (the factor kernels + sr_gram_kernel twice); naqs_net_sr_gram (the same
-+ row sums and centring); the two float64 Cholesky solves (torch); naqs_net_sr_direction (seeds + the training backward).
++ row sums and centring); the two float64 Cholesky solves, by torch and by naqs_net_sr_solve — measured alternately in the same
+call, three rounds, each repetition on fresh copies of T because the solve overwrites it (the copies are outside the timed
+region); naqs_net_sr_direction (seeds + the training backward).
 sr_gram_kernel's share of the f64-MFMA peak is computed from the uncentred call (an upper bound of the kernel's time); run under
 `rocprofv3 --kernel-trace --stats -- python tools/sr_bench.py --rows 1500` for the per-kernel split.
 """
@@ -50,6 +53,22 @@ def _timed(fn, reps):
     return 1e3 * a.elapsed_time(b) / reps, out
 
 
+def _timed_fresh(fn, fresh, reps):
+    """Mean microseconds of fn(*fresh()) over reps calls, each on fresh arguments made outside the timed region."""
+    fn(*fresh())
+    torch.cuda.synchronize()
+    total = 0.0
+    for _ in range(reps):
+        args = fresh()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = fn(*args)
+        b.record()
+        torch.cuda.synchronize()
+        total += a.elapsed_time(b)
+    return 1e3 * total / reps, out
+
+
 def gram_flops(P, Ha, phase, M):
     """Multiply-adds x 2 of sr_gram_kernel's products over the upper triangle of 64 x 64 tiles (both blocks): per amplitude pair
     the depths 32 (d-out) + Ha (h) + Ha (d-pre) + 32 (x), per phase layer its padded output and input widths."""
@@ -80,10 +99,33 @@ def step_calls(rows, reps):
         return [torch.cholesky_solve(y.unsqueeze(1), torch.linalg.cholesky_ex(T)[0]).squeeze(1) for T, y in ((Ta, ya), (Tp, yp))]
 
     t_solve, (xa, xp) = _timed(solves, max(1, reps // 4))
+    # the two solvers alternately, three rounds, every repetition on fresh copies of T (naqs_net_sr_solve overwrites it; torch's
+    # path gets the same copies so that both are measured alike)
+    from naqs_amd import _lib
+    lib = _lib.load_library()
+    fresh = lambda: (Ta.clone(), Tp.clone())
+    torch_solves = lambda A, P: [torch.cholesky_solve(y.unsqueeze(1), torch.linalg.cholesky_ex(T)[0]).squeeze(1) for T, y in ((A, ya), (P, yp))]
+    hip_solves = lambda A, P: fused.sr_solve(A, P, ya, yp)
+    rounds_torch, rounds_hip = [], []
+    for _ in range(3):
+        rounds_torch.append(_timed_fresh(torch_solves, fresh, max(1, reps // 4))[0])
+        t, (ha, hp, info) = _timed_fresh(hip_solves, fresh, max(1, reps // 4))
+        rounds_hip.append(t)
+    n0 = lib.naqs_launch_count()
+    hip_solves(*fresh())
+    solve_launches = lib.naqs_launch_count() - n0
+    assert info.tolist() == [0, 0]
+    solve_flops = 2.0 * (rows ** 3 / 3.0 + 2.0 * rows ** 2)
+    hip_vs_torch = [float(((h - x).abs().max() / x.abs().max()).item()) for h, x in ((ha, xa), (hp, xp))]
     t_dir, _ = _timed(lambda: fused.sr_direction(saved, w, xa, xp), reps)
     flops = gram_flops(hil.N // 2, 64, (512, 512), rows)
     return dict(what="N2 natural-gradient step, per call", rows=rows, us_forward=t_fwd, us_factors_and_gram=t_unc,
                 us_gram_and_centring=t_gram, us_two_cholesky_solves=t_solve, us_direction=t_dir,
+                us_two_cholesky_solves_rounds=rounds_torch, us_two_hip_solves_rounds=rounds_hip,
+                us_two_hip_solves=float(np.median(rounds_hip)), hip_solve_launches=int(solve_launches),
+                us_step_hip=t_fwd + t_gram + float(np.median(rounds_hip)) + t_dir, solve_gflop=solve_flops / 1e9,
+                hip_solve_fraction_of_f64_mfma_peak=solve_flops / (float(np.median(rounds_hip)) * 1e-6) / PEAK_F64_MFMA,
+                hip_vs_torch_max_rel_diff=hip_vs_torch,
                 us_step=t_fwd + t_gram + t_solve + t_dir, gram_gflop=flops / 1e9,
                 gram_fraction_of_f64_mfma_peak_lower_bound=flops / (t_unc * 1e-6) / PEAK_F64_MFMA)
 
@@ -127,9 +169,10 @@ def main():
     ap.add_argument("--n-samples", type=float, default=1e6)
     ap.add_argument("--sr-shift", type=float, default=1e-3)
     ap.add_argument("--sr-lr", type=float, default=0.1)
+    ap.add_argument("--sr-solver", choices=["torch", "hip"], default=None)
     a = ap.parse_args()
     if a.converge:
-        for ng in (dict(diag_shift=a.sr_shift, lr=a.sr_lr), None):
+        for ng in (dict(dict(diag_shift=a.sr_shift, lr=a.sr_lr), **({"solver": a.sr_solver} if a.sr_solver else {})), None):
             print(json.dumps(converge(a.converge, a.target, a.max_steps, ng, int(a.n_samples))), flush=True)
         return
     for rows in (int(r) for r in a.rows.split(",")):
