@@ -17,6 +17,12 @@ on the CPU is an exact-arithmetic stand-in for what the HIP backward computes in
 * ``conditionals_f64``         one block's four conditional probabilities for a set of prefixes (the sampler's tree nodes);
 * ``SECTORS`` / ``sector_net`` one electron sector per orbital-pair count P = 2..16 and a default-initialised network on it;
 * ``random_keys``              distinct random physical keys of any sector;
+* ``anchor`` / ``rebalance`` / ``outlier_unit`` / ``grown``
+                               recipes that take a default-initialised network to the regime of a trained one: |psi|^2
+                               peaked on one determinant, weights of unequal magnitude within a block, a unit that sets
+                               a block's maxima and never fires, grown weights;
+* ``tree_levels`` / ``tree_chi2``
+                               the sampling tree of one draw and its level-by-level multinomial test;
 * ``pair_ordering`` / ``relabel_keys`` / ``model_index``
                                qubit orderings other than -1: a seeded spin-preserving pair permutation as a
                                ``qubit2model`` list, the same model-order bits under another ordering, and the rank of a
@@ -256,6 +262,157 @@ def random_keys(hil, M, seed):
         kb = (np.uint64(1) << (2 * b[:, :nb] + 1).astype(np.uint64)).sum(1, dtype=np.uint64)
         keys = np.unique(np.concatenate([keys, ka | kb]))
     return rs.permutation(keys)[:M]
+
+
+# ------------------------------------------------------------------------------------------------- peaked networks
+def _anchor_occ(wf):
+    """Per model pair the anchor's outcome (0 empty, 1 alpha only, 3 both) and the amplitude output that feeds it alone:
+    the last n_beta pairs doubly occupied (output 2), n_alpha - n_beta pairs before them singly (output 1), the rest empty
+    (output 0).  Outputs 0 and 2 enter one outcome each with or without the spin symmetrisation; output 1 feeds |10> (and,
+    symmetrised, |01>)."""
+    m = wf.model
+    assert m.use_restricted_hilbert and m.use_amp_spin_sym and m.n_alpha_up >= m.n_beta_up
+    P, na, nb = m.P, m.n_alpha_up, m.n_beta_up
+    return [0] * (P - na) + [1] * (na - nb) + [3] * nb, [0] * (P - na) + [1] * (na - nb) + [2] * nb
+
+
+def anchor(wf, B, open_shell=False):
+    """Add the bias ``B`` to the amplitude output of every block that feeds the anchor determinant's outcome: |psi|^2 peaks on
+    that determinant (one softmax logit 2 B above the others per pair) -> the anchor key (uint64, qubit order of the
+    network's qubit_ordering).  Closed-shell sectors unless ``open_shell``: there the n_alpha - n_beta singly occupied
+    pairs get the bias on output 1, shared by |10> and |01>, and the key returned is the alpha one."""
+    m = wf.model
+    assert open_shell or m.n_alpha_up == m.n_beta_up, "anchor: a closed-shell sector (open_shell=True for the other form)"
+    occ, outs = _anchor_occ(wf)
+    q2m = [int(q) for q in wf.qubit2model_permutation]
+    key = 0
+    with torch.no_grad():
+        for n, (o, j) in enumerate(zip(occ, outs)):
+            m.amp_layers[n].linears()[-1].bias[j] += B
+            if o & 1:
+                key |= 1 << q2m[2 * n]
+            if o & 2:
+                key |= 1 << q2m[2 * n + 1]
+    return np.uint64(key)
+
+
+def _parts(wf, part):
+    """``part`` -> the lists of (lower Linear, upper Linear) it names: ("amp", n[, l]) hidden layer l of amplitude block n;
+    ("phase", l) hidden layer l of every phase block (the single MLP, or each aggregate block)."""
+    m = wf.model
+    if part[0] == "amp":
+        lin = m.amp_layers[part[1]].linears()
+        l = part[2] if len(part) > 2 else 0
+        return [(lin[l], lin[l + 1])]
+    assert part[0] == "phase"
+    return [(blk.linears()[part[1]], blk.linears()[part[1] + 1]) for blk in m.phase_layers]
+
+
+def rebalance(wf, k, part):
+    """relu(2^k x) = 2^k relu(x): W_l, b_l of ``part`` times 2^k and W_{l+1} times 2^-k (b_{l+1} untouched) is the same
+    function, and — a power of two commutes with every float32 rounding short of under- and overflow — the same float32
+    bits.  -> (names of the parameters multiplied by 2^k, names multiplied by 2^-k): their gradients are the original's
+    times 2^-k and 2^k."""
+    names = {id(p): n for n, p in wf.model.named_parameters()}
+    up, down = [], []
+    with torch.no_grad():
+        for lo, hi in _parts(wf, part):
+            lo.weight.mul_(2.0 ** k)
+            lo.bias.mul_(2.0 ** k)
+            hi.weight.mul_(2.0 ** -k)
+            up += [names[id(lo.weight)], names[id(lo.bias)]]
+            down.append(names[id(hi.weight)])
+    return up, down
+
+
+def outlier_unit(wf, R):
+    """Hidden unit 0 of every amplitude block's first layer: its W1 row times ``R`` and b1[0] = -2 R sum_k |W1[0][k]| (the
+    inputs are +-1 or 0: the unit never fires), its W2 column unchanged.  The network is the same function; the unit sets
+    the first layer's weight maximum and the largest pre-activation bound of the block.  -> names of the tensors it touched."""
+    names = {id(p): n for n, p in wf.model.named_parameters()}
+    out = []
+    with torch.no_grad():
+        for blk in wf.model.amp_layers:
+            lin = blk.linears()[0]
+            lin.bias[0] = -2.0 * R * lin.weight[0].abs().sum()
+            lin.weight[0].mul_(R)
+            out += [names[id(lin.weight)], names[id(lin.bias)]]
+    return out
+
+
+def grown(wf, out_factor=4.0, hidden_factor=2.0, B=6.0):
+    """Every block's output layer (weights and bias) times ``out_factor``, every hidden layer times ``hidden_factor``, then
+    ``anchor(B)``: weights that have left U(+-1/sqrt(fan_in)) -> the anchor key."""
+    with torch.no_grad():
+        for blk in list(wf.model.amp_layers) + list(wf.model.phase_layers):
+            lin = blk.linears()
+            for l, layer in enumerate(lin):
+                f = out_factor if l == len(lin) - 1 else hidden_factor
+                layer.weight.mul_(f)
+                layer.bias.mul_(f)
+    return anchor(wf, B)
+
+
+# ------------------------------------------------------------------------------------ the sampling tree of one draw
+def tree_levels(wf64, hil, k, c):
+    """The sampling tree of one draw (keys ``k``, counts ``c``): per level, each node's children counts [U, 4], float64
+    conditionals [U, 4] and physical mask [U, 4]."""
+    st = hil.idx2state(torch.as_tensor(np.asarray(k).astype(np.int64)))
+    ms = st[:, wf64._q2m.cpu()]
+    occ = ((ms[:, 0::2] > 0).long() + 2 * (ms[:, 1::2] > 0).long()).numpy().astype(np.int64)
+    code = np.zeros(len(k), np.int64)
+    levels = []
+    for n in range(occ.shape[1]):
+        _, first, inv = np.unique(code, return_index=True, return_inverse=True)
+        cc = np.zeros((len(first), 4))
+        np.add.at(cc, (inv.reshape(-1), occ[:, n]), c)
+        levels.append((cc,) + conditionals_f64(wf64, st[first], n))
+        code = code + occ[:, n] * (4 ** n)
+    return levels
+
+
+def tree_chi2(levels, root=None, replace=None, min_lump=0.0):
+    """Level-by-level test: every node's count splits into children counts ~ Multinomial(count, p), p the node's float64
+    conditionals; cells of >= 5 expected draws, the rest of a node pooled; a node left with one cell is skipped.
+    -> (pooled chi2, dof, p-value, per-level p-values, draws of masked children, per-level share of the draws in skipped
+    nodes that have two or more physical children [a node whose electron budget leaves one child has nothing to test]).
+    ``root``: the root's p replaced; ``replace``: (level, node, p) one node's p replaced.  ``min_lump``: a pooled cell
+    expecting fewer draws than this joins the node's smallest cell of >= 5 (on a peaked tree a node of 10^5 draws has
+    children expecting 10^-3: one draw there is a chi-square term of 10^3 the chi-square law does not describe).
+    For FULL masking, which drops no draw (nade.py:695)."""
+    from scipy import stats
+    tot, dof, per_level, masked_hits, skipped = 0.0, 0, [], 0, []
+    for n, (cc, pc, phys) in enumerate(levels):
+        if n == 0 and root is not None:
+            pc = root[None, :]
+        if replace is not None and replace[0] == n:
+            pc = pc.copy()
+            pc[replace[1]] = replace[2]
+        masked_hits += int(cc[pc == 0].sum())
+        e = cc.sum(1, keepdims=True) * pc
+        node_draws = cc.sum(1)
+        big = e >= 5
+        chi = np.where(big, (cc - e) ** 2 / np.where(big, e, 1), 0).sum(1)
+        so, se = np.where(big, 0, cc).sum(1), np.where(big, 0, e).sum(1)
+        if min_lump > 0:
+            join = (se > 0) & (se < min_lump) & big.any(1)
+            j = np.where(big, e, np.inf).argmin(1)
+            rows = np.flatnonzero(join)
+            cc, e = cc.copy(), e.copy()
+            cc[rows, j[rows]] += so[rows]
+            e[rows, j[rows]] += se[rows]
+            so, se = np.where(join, 0, so), np.where(join, 0, se)
+            chi = np.where(big, (cc - e) ** 2 / np.where(big, e, 1), 0).sum(1)
+        lump = se > 0
+        chi += np.where(lump, (so - se) ** 2 / np.where(lump, se, 1), 0)
+        cells = big.sum(1) + lump
+        keep = cells >= 2
+        lv_chi, lv_dof = chi[keep].sum(), int((cells[keep] - 1).sum())
+        per_level.append(stats.chi2.sf(lv_chi, lv_dof) if lv_dof else 1.0)
+        skipped.append(node_draws[~keep & (phys.sum(1) >= 2)].sum() / max(node_draws.sum(), 1))
+        tot += lv_chi
+        dof += lv_dof
+    return tot, dof, stats.chi2.sf(tot, dof) if dof else 1.0, per_level, masked_hits, skipped
 
 
 def pair_ordering(P, seed):

@@ -435,43 +435,12 @@ def test_sampler_exact_chi2(name, variant):
 
 
 def _tree_levels(wf64, hil, k, c):
-    """The sampling tree of one draw: per level, each node's children counts [U, 4] and float64 conditionals [U, 4]."""
-    st = _states(hil, k)
-    ms = st[:, wf64._q2m.cpu()]
-    occ = ((ms[:, 0::2] > 0).long() + 2 * (ms[:, 1::2] > 0).long()).numpy().astype(np.int64)
-    code = np.zeros(len(k), np.int64)
-    levels = []
-    for n in range(occ.shape[1]):
-        _, first, inv = np.unique(code, return_index=True, return_inverse=True)
-        cc = np.zeros((len(first), 4))
-        np.add.at(cc, (inv.reshape(-1), occ[:, n]), c)
-        levels.append((cc, gr.conditionals_f64(wf64, st[first], n)[0]))
-        code = code + occ[:, n] * (4 ** n)
-    return levels
+    return gr.tree_levels(wf64, hil, k, c)
 
 
 def _tree_chi2(levels, root=None):
-    """Level-by-level test under FULL masking (no draw is dropped, nade.py:695): every node's count splits into children
-    counts ~ Multinomial(count, p), p the node's float64 conditionals; cells of >= 5 expected draws, the rest of a node pooled.
-    -> (pooled chi2, dof, p-value, per-level p-values, draws of masked children).  ``root``: the root's p replaced."""
-    tot, dof, per_level, masked_hits = 0.0, 0, [], 0
-    for n, (cc, pc) in enumerate(levels):
-        if n == 0 and root is not None:
-            pc = root[None, :]
-        masked_hits += int(cc[pc == 0].sum())
-        e = cc.sum(1, keepdims=True) * pc
-        big = e >= 5
-        chi = np.where(big, (cc - e) ** 2 / np.where(big, e, 1), 0).sum(1)
-        so, se = np.where(big, 0, cc).sum(1), np.where(big, 0, e).sum(1)
-        lump = se > 0
-        chi += np.where(lump, (so - se) ** 2 / np.where(lump, se, 1), 0)
-        cells = big.sum(1) + lump
-        keep = cells >= 2
-        lv_chi, lv_dof = chi[keep].sum(), int((cells[keep] - 1).sum())
-        per_level.append(stats.chi2.sf(lv_chi, lv_dof) if lv_dof else 1.0)
-        tot += lv_chi
-        dof += lv_dof
-    return tot, dof, stats.chi2.sf(tot, dof), per_level, masked_hits
+    """grad_reference.tree_chi2 (FULL masking: no draw is dropped)."""
+    return gr.tree_chi2(levels, root=root)[:5]
 
 
 @pytest.mark.parametrize("name", ["BeH2", "Li2O", "syn32_8_8"])
