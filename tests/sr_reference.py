@@ -12,7 +12,11 @@ Definitions (include/naqs_hip.h, naqs_net_sr_gram): log psi_i = a_i + i phi_i, A
                                          reference; float32: the yardstick, its rows taken to float64 before any product);
 * ``gram_err``                           max_ij |G - G64|_ij / sqrt(G64_ii G64_jj);
 * ``system`` / ``direction``             the definitions above in float64 numpy (dense solve);
-* ``direction_f32``                      the same step as a float32 network on the CPU takes it: the direction's yardstick.
+* ``direction_f32``                      the same step as a float32 network on the CPU takes it: the direction's yardstick;
+* ``LARGE_CASES`` / ``sampled_rows`` / ``rows_below`` / ``seeds_f64`` / ``WIDTH_CASES``
+                                         tables of up to 4 300 rows (tests/test_sr_scale_gpu.py): G_ij depends on rows i and j
+                                         alone, so the float64 Jacobian rows of ~80 sampled rows check G[R][:, R] at any M; the
+                                         centring is ``centred`` of the device's own G; X^T x is one float64 backward with seeds.
 """
 import numpy as np
 import torch
@@ -38,6 +42,50 @@ CASES = [
     ("syn32_8_8", True, 64, (32,), False, "PARTIAL"),
 ]
 ROWS = (1, 63, 64, 65, 200)     # the tile edge, padded rows, I = J and I < J tiles; capped by the sector's size (H2: 4, syn10_3_2: 100)
+
+
+# The same step at the table sizes a run on N2 has (tests/test_sr_scale_gpu.py).  LiF single: 44 100 states and N_p = 3 206 < M, T is
+# rank-deficient and the shift carries the factorisation; LiF aggregate: Ha = 128 amplitude blocks (8 waves), P = 10; syn32_8_8:
+# P = 16 (32 jobs = SR_MAX_JOBS), bit 31 of the keys, grad_in_kernel in the phase chain.
+LARGE_CASES = [
+    ("LiF", False, 16, (32,), True, "PARTIAL"),
+    ("LiF", True, 128, (32,), True, "PARTIAL"),
+    ("syn32_8_8", False, 64, (64, 64), True, "PARTIAL"),
+]
+LARGE_ROWS = 4300                                           # 67 full 64-row tiles and one of 12 rows
+LARGE_SIZES = (1023, 1024, 1025, 4095, 4096, 4097, 4300)    # the scratch's first capacity (1 024), the tile loop's second trip (64 x 64)
+FIXED_ROWS = (0, 63, 64, 255, 256, 257, 1022, 1023, 1024, 1025, 4094, 4095, 4096, 4097, 4299)
+
+# amplitude widths beside 16 and 64: 2, 3, 6 and 8 waves per workgroup of sr_amp_factors_kernel; kh = 32, 64, 96, 128 of ldh = 64, 64,
+# 128, 128 columns (48, like 16, leaves padding columns inside the products' reach)
+WIDTH_CASES = [("LiH", agg, ha, (32,), True, "PARTIAL") for agg in (False, True) for ha in (32, 48, 96, 128)]
+WIDTH_ROWS = (65, 200)
+
+
+def sampled_rows(n=LARGE_ROWS, extra=64, seed=11):
+    """R_all: FIXED_ROWS and ``extra`` seeded random rows of a table of ``n`` rows, ascending."""
+    rs = np.random.RandomState(seed)
+    return np.unique(np.concatenate([np.asarray(FIXED_ROWS), rs.choice(n, extra, replace=False)]))
+
+
+def rows_below(R_all, M):
+    """The sampled rows of the leading M rows together with the last row M - 1 (FIXED_ROWS holds it for every size of
+    LARGE_SIZES) -> (rows, their positions in R_all)."""
+    rows = np.unique(np.concatenate([R_all[R_all < M], [M - 1]]))
+    pos = np.searchsorted(R_all, rows)
+    assert np.array_equal(R_all[pos], rows), M
+    return rows, pos
+
+
+def seeds_f64(w, x):
+    """s_i = sqrt(w_i) x_i - w_i sum_j sqrt(w_j) x_j in float64: X^T x is the backward pass with these seeds."""
+    sw = np.sqrt(w)
+    return sw * x - w * (sw @ x)
+
+
+def flat(wf, grads):
+    """A {name: array} of per-parameter arrays -> one float64 vector in state_dict order."""
+    return np.concatenate([np.asarray(grads[n], np.float64).reshape(-1) for n, _ in wf.model.named_parameters()])
 
 
 def case_id(case):
@@ -138,7 +186,12 @@ def direction_f32(w32, states, A32, B32, w, g, diag_shift):
 def per_tensor_err(wf, got, want):
     """max over the parameter tensors of max |got - want| / max |want| on the tensor's slice of the flat vectors (the backward
     tests' measure; a tensor whose reference slice is zero — pair 0's first-layer weights see a constant-zero input — must be zero)."""
-    worst, off = 0.0, 0
+    return per_tensor_worst(wf, got, want)[0]
+
+
+def per_tensor_worst(wf, got, want):
+    """``per_tensor_err`` and the name of the tensor that sets it."""
+    worst, who, off = 0.0, None, 0
     got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
     for name, p in wf.model.named_parameters():
         n = p.numel()
@@ -148,5 +201,7 @@ def per_tensor_err(wf, got, want):
         if scale == 0:
             assert np.all(a == 0), name
             continue
-        worst = max(worst, float(np.abs(a - b).max() / scale))
-    return worst
+        err = float(np.abs(a - b).max() / scale)
+        if err > worst or who is None:
+            worst, who = err, name
+    return worst, who

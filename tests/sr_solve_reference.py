@@ -11,7 +11,7 @@ right-hand side carried as one more row, then the back substitution block by blo
 Measures, in np.longdouble on the host, u = 2^-53:
     eta = |T x - y|_inf / (|T|_inf |x|_inf + |y|_inf)          normwise backward error of the solution
     rho = |L L^T - T|_inf / |T|_inf                            backward error of the factor (L: the returned lower triangle;
-                                                               T symmetric)
+                                                               T symmetric); ``rho_rows``: the numerator on sampled rows
     fwd = |x - x_lapack|_inf / |x_lapack|_inf                  against scipy.linalg.cho_solve on the CPU
 Bounds: eta, rho <= max(M, 16) u (far inside Cholesky's worst-case theory, gamma_{3M+1} M); fwd <= cond_2(T) max(M, 16) u.
 LAPACK and the blocked model sit at eta <= 6.5e-17 over the tests' 33 size / shift cases; one float32 rounding anywhere in the
@@ -71,6 +71,20 @@ def rho(T, L):
             E[i:i + B, j:j + B] = Ll[i:i + B, :j + B] @ Ll[j:j + B, :j + B].T - Tl[i:i + B, j:j + B]
             E[j:j + B, i:i + B] = E[i:i + B, j:j + B].T
     return float(_inf(E) / _inf(Tl))
+
+
+def rho_rows(T, L, rows):
+    """rho on sampled rows, for sizes where the whole product is too slow in longdouble: |L[rows] L^T - T[rows]|_inf / |T|_inf
+    (L as for ``rho``; the norm of the numerator is the largest row sum over ``rows``)."""
+    rows = np.asarray(rows)
+    worst = np.longdouble(0)
+    for r in rows:                            # row r of L L^T: L[r, :r + 1] against the first r + 1 columns of every row
+        lr = np.asarray(L[r, :r + 1], np.longdouble)
+        Lc = np.array(L[:, :r + 1], np.longdouble)
+        Lc[:r + 1] = np.tril(Lc[:r + 1])      # (the strict upper triangle is ignored)
+        worst = max(worst, np.abs(Lc @ lr - np.asarray(T[r], np.longdouble)).sum())
+    tnorm = max(np.abs(np.asarray(T[i:i + 256], np.longdouble)).sum(1).max() for i in range(0, len(T), 256))
+    return float(worst / tnorm)
 
 
 def fwd(x, x_ref):
