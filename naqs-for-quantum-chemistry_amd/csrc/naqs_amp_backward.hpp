@@ -2,7 +2,9 @@
 // amp_backward_kernel (naqs_grad.hip) and the training step's fused backward launch (naqs_phase_grad.hip:
 // backward_mega_kernel).  See naqs_grad.hip for the formulation.
 #pragma once
+#include <algorithm>
 #include <cstdint>
+#include <type_traits>
 
 #include "naqs_common.hpp"
 #include "naqs_net.hpp"
@@ -32,34 +34,129 @@ struct AmpSrc { int64_t off[MAXP]; };     // flat (state_dict) offset of pair n'
 // (Rounds 1-2: 256-sample tiles with thread = sample walking ALL hidden units — a serial chain of Ha LDS-fed iterations per
 // thread, twice: 37 us for the one tile a workgroup gets at M ~ 1 200, whatever the tile size, and 2 x 67 us for 128-unit
 // blocks.  Splitting the units over the waves cuts the chain by Ha / 16 and gives four times as many workgroups.)
-// smem: weights | d-pre tile [Ha][65] | h tile [Ha][65] | d-out [5][64] | input bits [64] | partial outputs [Ha/16][5][64]
+// Stage (1) is stage1_tile, which the natural gradient's factor kernel (naqs_sr.hip: sr_amp_factors_kernel) runs too; stage (2)
+// is amp_backward_pair's own.
 // raw: phase blocks of an aggregate-phase network (d describes them: 4 outputs, no symmetry) — the differentiated
 // quantity is the raw output of the realised outcome, d out[c] = g_i [c == occ], no conditional in between.
 constexpr int GT = 64;                                    // samples per tile = lanes of a wave
+constexpr int LD = GT + 1;                                // row stride of the d-pre and h tiles
+constexpr int MAX_DYN_LDS = 156 * 1024;                   // bytes of dynamic LDS the block kernels are allowed (and may ask for)
+inline int tile_wgs(const int64_t M) { return (int)std::min<int64_t>(MAX_TILE_WGS, (M + GT - 1) / GT); }   // workgroups per pair for M samples
+
+// The tile's LDS layout, as float offsets into the workgroup's dynamic LDS for Ha hidden units and packed rows of S floats:
+// weights (Ha rows, b2 [8]) at 0 | d-pre tile [Ha][LD] | h tile [Ha][LD] | d-out [5][GT] | input bits [GT] | partial outputs
+// [Ha / 16][5][GT]
+struct TileLds { int dpre, h, dout, x, part, floats; };
+constexpr __host__ __device__ TileLds tile_lds(const int Ha, const int S) {
+    TileLds T{};
+    T.dpre = (Ha * S + 8 + 3) & ~3;
+    T.h = T.dpre + Ha * LD;
+    T.dout = T.h + Ha * LD;
+    T.x = T.dout + 5 * GT;
+    T.part = T.x + GT;
+    T.floats = T.part + (Ha >> 4) * 5 * GT;
+    return T;
+}
+
+// pair NB's packed weights -> LDS (the caller's barrier follows)
+template <int NB>
+__device__ __forceinline__ void stage_weights(const NetDims &d, const float *__restrict__ w, float *smem) {
+    constexpr int S = amp_row_stride(NB == 0 ? 1 : 2 * NB);
+    const f32x4 *from = reinterpret_cast<const f32x4 *>(w + d.amp_off[NB]);
+    f32x4 *to = reinterpret_cast<f32x4 *>(smem);
+    for (int e = threadIdx.x; e < (d.Ha * S + 8) / 4; e += (d.Ha >> 4) * WAVE) to[e] = from[e];
+}
+
+// Stage (1) for the tile whose first sample is t0, from the key load to the barrier behind the d-pre tile: fills the h tile, the
+// d-pre tile, d-out and the input bits (bit NIN: the bias input) and returns the lane's d-out.  The seed of sample i is
+// g[i * g_stride] (g_stride 2: a column of the loss gradient [M][2]).
+template <int NB>
+__device__ __forceinline__ void stage1_tile(const NetDims &d, float *smem, const int64_t M, const uint64_t *__restrict__ keys,
+                                            const float *__restrict__ g, const int g_stride, const int raw, const int64_t t0,
+                                            float (&dout)[5]) {
+    constexpr int NIN = NB == 0 ? 1 : 2 * NB;
+    constexpr int S = amp_row_stride(NIN);
+    const int Ha = d.Ha, nout = d.n_out_amp, NW = Ha >> 4;
+    const TileLds T = tile_lds(Ha, S);
+    float *s_w = smem, *s_dpre = smem + T.dpre, *s_h = smem + T.h, *s_do = smem + T.dout, *s_part = smem + T.part;
+    uint32_t *s_x = reinterpret_cast<uint32_t *>(smem + T.x);
+    const float *b2 = s_w + Ha * S;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int j0 = wave * 16;                              // this wave's hidden units
+    const int64_t i = t0 + lane;
+    const bool valid = i < M;
+    const uint64_t key = valid ? keys[i] : 0ull;
+    const auto [abits, bbits, occ] = naqs::key_pair_view(d, NB, key);
+    const bool swap = (raw ? d.phase_sym != 0 : d.sym != 0) && abits > bbits;      // (raw: the phase blocks' spin-ordered inputs)
+    const uint32_t first = swap ? bbits : abits, second = swap ? abits : bbits;
+    float x[NIN];
+    if (NB == 0) {
+        x[0] = 0.0f;                                       // pair 0 sees a constant-zero input (nade.py:509-511)
+    } else {
+#pragma unroll
+        for (int k = 0; k < NB; ++k) {
+            x[k] = ((first >> k) & 1u) ? 1.0f : -1.0f;
+            x[NB + k] = ((second >> k) & 1u) ? 1.0f : -1.0f;
+        }
+    }
+    const float gi = valid ? g[i * g_stride] : 0.0f;
+    // forward of this wave's 16 hidden units; the activations go to their tile, the partial outputs to LDS
+    float o[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll 2
+    for (int jj = j0; jj < j0 + 16; ++jj) {
+        float rv[S];
+        naqs::load_row<S>(s_w + jj * S, rv);
+        float h0 = rv[NIN], h1 = 0.0f;
+#pragma unroll
+        for (int k = 0; k + 1 < NIN; k += 2) { h0 = fmaf(rv[k], x[k], h0); h1 = fmaf(rv[k + 1], x[k + 1], h1); }
+        if (NIN & 1) h0 = fmaf(rv[NIN - 1], x[NIN - 1], h0);
+        const float h = fmaxf(h0 + h1, 0.0f);
+        s_h[jj * LD + lane] = h;
+#pragma unroll
+        for (int c = 0; c < 5; ++c)
+            if (c < nout) o[c] = fmaf(rv[NIN + 1 + c], h, o[c]);
+    }
+#pragma unroll
+    for (int c = 0; c < 5; ++c) s_part[(wave * 5 + c) * GT + lane] = o[c];
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < 5; ++c) {
+        float v = c < nout ? b2[c] : 0.0f;
+        for (int q = 0; q < NW; ++q) v += s_part[(q * 5 + c) * GT + lane];                // fixed order: wave 0 first
+        o[c] = v;
+    }
+    naqs::amp_block_delta(d, NB, raw != 0, o, abits, bbits, occ, valid, gi, dout);
+    if (wave == 0) {                                       // (every wave computed the same d-out; one copy for the GEMMs)
+#pragma unroll
+        for (int c = 0; c < 5; ++c) s_do[c * GT + lane] = dout[c];
+        s_x[lane] = (NB == 0 ? 0u : (first | (second << NB))) | (1u << NIN);
+    }
+    // d pre-activations of this wave's units -> tile (h > 0 <=> pre > 0); W2[:][jj] sits at floats NIN+1.. of the packed row
+#pragma unroll 4
+    for (int jj = j0; jj < j0 + 16; ++jj) {
+        const float *row = s_w + jj * S + NIN + 1;
+        float dh = 0.0f;
+#pragma unroll
+        for (int c = 0; c < 5; ++c)
+            if (c < nout) dh = fmaf(row[c], dout[c], dh);
+        s_dpre[jj * LD + lane] = s_h[jj * LD + lane] > 0.0f ? dh : 0.0f;
+    }
+    __syncthreads();
+}
+
 template <int NB>
 __device__ __forceinline__ void amp_backward_pair(const NetDims &d, const float *__restrict__ w, const int64_t M,
                                                   const uint64_t *__restrict__ keys, const float *__restrict__ g,
                                                   float *__restrict__ out, float *smem, const int raw, const int wg,
                                                   const int n_wgs, const int g_stride) {
     constexpr int NIN = NB == 0 ? 1 : 2 * NB;
-    constexpr int S = amp_row_stride(NIN);
     constexpr int RT = (NIN + 1 + 15) / 16;               // 16-row tiles of the input axis (inputs + the bias input)
-    constexpr int LD = GT + 1;
-    const int Ha = d.Ha, nout = d.n_out_amp, NW = Ha >> 4, NT = NW * WAVE;
-    const int w_floats = (Ha * S + 8 + 3) & ~3;
-    float *s_w = smem;
-    float *s_dpre = s_w + w_floats;
-    float *s_h = s_dpre + Ha * LD;
-    float *s_do = s_h + Ha * LD;                          // [5][GT]
-    uint32_t *s_x = reinterpret_cast<uint32_t *>(s_do + 5 * GT);
-    float *s_part = reinterpret_cast<float *>(s_x + GT);  // [NW][5][GT]
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), m = lane & 15, kq = lane >> 4;
-    {
-        const f32x4 *from = reinterpret_cast<const f32x4 *>(w + d.amp_off[NB]);
-        f32x4 *to = reinterpret_cast<f32x4 *>(s_w);
-        for (int e = tid; e < (Ha * S + 8) / 4; e += NT) to[e] = from[e];
-    }
-    const float *b2 = s_w + Ha * S;
+    const int Ha = d.Ha, nout = d.n_out_amp;
+    const TileLds T = tile_lds(Ha, amp_row_stride(NIN));
+    const float *s_dpre = smem + T.dpre, *s_h = smem + T.h, *s_do = smem + T.dout;
+    const uint32_t *s_x = reinterpret_cast<const uint32_t *>(smem + T.x);
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), m = lane & 15, kq = lane >> 4;
+    stage_weights<NB>(d, w, smem);
     const int j0 = wave * 16;                              // this wave's hidden units
     f32x4 acc1[RT], acc2 = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -68,98 +165,10 @@ __device__ __forceinline__ void amp_backward_pair(const NetDims &d, const float 
     __syncthreads();
 
     for (int64_t t0 = (int64_t)wg * GT; t0 < M; t0 += (int64_t)n_wgs * GT) {
-        const int64_t i = t0 + lane;
-        const bool valid = i < M;
-        const uint64_t key = valid ? keys[i] : 0ull;
-        uint32_t abits = 0, bbits = 0;
+        float dout[5];
+        stage1_tile<NB>(d, smem, M, keys, g, g_stride, raw, t0, dout);
 #pragma unroll
-        for (int k = 0; k < NB; ++k) {
-            abits |= (uint32_t)((key >> d.qa[k]) & 1ull) << k;
-            bbits |= (uint32_t)((key >> d.qb[k]) & 1ull) << k;
-        }
-        const int occ = (int)((key >> d.qa[NB]) & 1ull) + 2 * (int)((key >> d.qb[NB]) & 1ull);
-        const bool swap = (raw ? d.phase_sym != 0 : d.sym != 0) && abits > bbits;      // (raw: the phase blocks' spin-ordered inputs)
-        const uint32_t first = swap ? bbits : abits, second = swap ? abits : bbits;
-        float x[NIN];
-        if (NB == 0) {
-            x[0] = 0.0f;                                   // pair 0 sees a constant-zero input (nade.py:509-511)
-        } else {
-#pragma unroll
-            for (int k = 0; k < NB; ++k) {
-                x[k] = ((first >> k) & 1u) ? 1.0f : -1.0f;
-                x[NB + k] = ((second >> k) & 1u) ? 1.0f : -1.0f;
-            }
-        }
-        const float gi = valid ? g[i * g_stride] : 0.0f;      // (g_stride 2: a column of the loss gradient [M][2])
-        // forward of this wave's 16 hidden units; the activations go to their tile, the partial outputs to LDS
-        float o[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll 2
-        for (int jj = j0; jj < j0 + 16; ++jj) {
-            float rv[S];
-            naqs::load_row<S>(s_w + jj * S, rv);
-            float h0 = rv[NIN], h1 = 0.0f;
-#pragma unroll
-            for (int k = 0; k + 1 < NIN; k += 2) { h0 = fmaf(rv[k], x[k], h0); h1 = fmaf(rv[k + 1], x[k + 1], h1); }
-            if (NIN & 1) h0 = fmaf(rv[NIN - 1], x[NIN - 1], h0);
-            const float h = fmaxf(h0 + h1, 0.0f);
-            s_h[jj * LD + lane] = h;
-#pragma unroll
-            for (int c = 0; c < 5; ++c)
-                if (c < nout) o[c] = fmaf(rv[NIN + 1 + c], h, o[c]);
-        }
-#pragma unroll
-        for (int c = 0; c < 5; ++c) s_part[(wave * 5 + c) * GT + lane] = o[c];
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < 5; ++c) {
-            float v = c < nout ? b2[c] : 0.0f;
-            for (int q = 0; q < NW; ++q) v += s_part[(q * 5 + c) * GT + lane];            // fixed order: wave 0 first
-            o[c] = v;
-        }
-        float da4[4];
-        if (raw) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) da4[c] = valid && c == naqs::phase_out_row(d, occ) ? gi : 0.0f;
-        } else {
-            float la[4];
-            bool ok[4];
-            naqs::amp_conditional<true>(d, NB, o, abits, bbits, la, ok);
-            // d la[occ] / d a4[c] = [c == occ] - softmax(2 a4)[c] on the allowed outcomes
-            const bool live = valid && (occ == 0 ? ok[0] : (occ == 1 ? ok[1] : (occ == 2 ? ok[2] : ok[3])));
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const float sm = ok[c] ? expf(2.0f * la[c]) : 0.0f;
-                da4[c] = live && ok[c] ? gi * ((c == occ ? 1.0f : 0.0f) - sm) : 0.0f;
-            }
-        }
-        float dout[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-        if (d.sym) {                                       // transpose of amp_symmetrise
-            const int x_order = abits > bbits ? 0 : (abits == bbits ? 1 : 2);
-            dout[0] = da4[0];
-            dout[2] = da4[3];
-            dout[1] = 0.5f * (da4[1] + da4[2]);
-            if (x_order == 1) dout[1] += 0.5f * (da4[1] + da4[2]);
-            else if (x_order == 0) { dout[3] = 0.5f * da4[1]; dout[4] = 0.5f * da4[2]; }
-            else { dout[4] = 0.5f * da4[1]; dout[3] = 0.5f * da4[2]; }
-        } else {
-            dout[0] = da4[0]; dout[1] = da4[1]; dout[2] = da4[2]; dout[3] = da4[3];
-        }
-        if (wave == 0) {                                   // (every wave computed the same d-out; one copy for the GEMMs)
-#pragma unroll
-            for (int c = 0; c < 5; ++c) { s_do[c * GT + lane] = dout[c]; accb2[c] += dout[c]; }
-            s_x[lane] = (NB == 0 ? 0u : (first | (second << NB))) | (1u << NIN);   // bit NIN: the bias input
-        }
-        // d pre-activations of this wave's units -> tile (h > 0 <=> pre > 0); W2[:][jj] sits at floats NIN+1.. of the packed row
-#pragma unroll 4
-        for (int jj = j0; jj < j0 + 16; ++jj) {
-            const float *row = s_w + jj * S + NIN + 1;
-            float dh = 0.0f;
-#pragma unroll
-            for (int c = 0; c < 5; ++c)
-                if (c < nout) dh = fmaf(row[c], dout[c], dh);
-            s_dpre[jj * LD + lane] = s_h[jj * LD + lane] > 0.0f ? dh : 0.0f;
-        }
-        __syncthreads();
+        for (int c = 0; c < 5; ++c) accb2[c] += dout[c];   // (every wave has the same d-out; wave 0's sums are written out)
         // sums over the tile's samples on the matrix cores: hidden tile ct = wave
         {
             const float *bd = s_dpre + (j0 + m) * LD + kq, *bh = s_h + (j0 + m) * LD + kq;
@@ -210,26 +219,24 @@ __device__ __forceinline__ void amp_backward_pair(const NetDims &d, const float 
     }
 }
 
-
 // floats of LDS one workgroup needs (any pair of the network)
-inline size_t smem_floats(const NetDims &d) {
-    const int nin_max = 2 * (d.P - 1);
-    const int S_max = amp_row_stride(nin_max);
-    const int NW = d.Ha >> 4;
-    return (size_t)((d.Ha * S_max + 8 + 3) & ~3) + 2 * (size_t)d.Ha * (GT + 1) + 5 * GT + GT + (size_t)NW * 5 * GT;
-}
+inline size_t smem_floats(const NetDims &d) { return (size_t)tile_lds(d.Ha, amp_row_stride(2 * (d.P - 1))).floats; }
 
-// all pairs: the switch over the compile-time pair index
-__device__ __forceinline__ void pair_dispatch(const int n, const NetDims &d, const float *__restrict__ w, const int64_t M,
-                                              const uint64_t *__restrict__ keys, const float *__restrict__ g, float *__restrict__ out,
-                                              float *smem, const int raw, const int wg, const int n_wgs, const int g_stride = 1) {
+// the switch over the compile-time pair index: f(std::integral_constant<int, NB>) for pair n
+template <typename F>
+__device__ __forceinline__ void for_pair(const int n, F &&f) {
     switch (n) {
-#define NAQS_CASE(NB) case NB: amp_backward_pair<NB>(d, w, M, keys, g, out, smem, raw, wg, n_wgs, g_stride); break;
+#define NAQS_CASE(NB) case NB: f(std::integral_constant<int, NB>{}); break;
         NAQS_CASE(0) NAQS_CASE(1) NAQS_CASE(2) NAQS_CASE(3) NAQS_CASE(4) NAQS_CASE(5) NAQS_CASE(6) NAQS_CASE(7)
         NAQS_CASE(8) NAQS_CASE(9) NAQS_CASE(10) NAQS_CASE(11) NAQS_CASE(12) NAQS_CASE(13) NAQS_CASE(14) NAQS_CASE(15)
 #undef NAQS_CASE
         default: break;
     }
+}
+__device__ __forceinline__ void pair_dispatch(const int n, const NetDims &d, const float *__restrict__ w, const int64_t M,
+                                              const uint64_t *__restrict__ keys, const float *__restrict__ g, float *__restrict__ out,
+                                              float *smem, const int raw, const int wg, const int n_wgs, const int g_stride = 1) {
+    for_pair(n, [&](auto nb) { amp_backward_pair<decltype(nb)::value>(d, w, M, keys, g, out, smem, raw, wg, n_wgs, g_stride); });
 }
 
 }  // namespace ampbw

@@ -233,54 +233,20 @@ __device__ __forceinline__ void amp_deep_backward_pair(const NetDims &d, const f
         const int64_t i = t0 + col;
         const bool valid = i < M;
         const uint64_t key = valid ? keys[i] : 0ull;
-        uint32_t abits = 0, bbits = 0;
-        for (int k = 0; k < n; ++k) {
-            abits |= (uint32_t)((key >> d.qa[k]) & 1ull) << k;
-            bbits |= (uint32_t)((key >> d.qb[k]) & 1ull) << k;
-        }
-        const int occ = (int)((key >> d.qa[n]) & 1ull) + 2 * (int)((key >> d.qb[n]) & 1ull);
+        const auto [abits, bbits, occ] = naqs::key_pair_view(d, n, key);
         float *outs = s_outs + wave * 128;
         amp_deep_item<CT, RAW>(d, wp, L, n, abits | (bbits << 16), lane, outs, s_h + 16 * wave, LD, layer);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (kq == 0 && RAW) {                               // lanes 0..15: d phase / d outputs of their sample
-            const float gi = valid ? g[i * g_stride] : 0.0f;
-            const int row = naqs::phase_out_row(d, occ);
-#pragma unroll
-            for (int c = 0; c < 8; ++c) s_do[c * DGT + col] = valid && c == row ? gi : 0.0f;
-            const bool swap = d.phase_sym && abits > bbits;
-            s_x[col] = (swap ? bbits : abits) | ((swap ? abits : bbits) << 16);
-        } else if (kq == 0) {                               // lanes 0..15: d log-amp / d outputs of their sample (as amp_backward_pair)
-            float o[5];
+        if (kq == 0) {                                      // lanes 0..15: d log-amp (RAW: d phase) / d outputs of their sample
+            float o[5], dout[5];
 #pragma unroll
             for (int c = 0; c < 5; ++c) o[c] = outs[s * 8 + c];
-            const float gi = valid ? g[i * g_stride] : 0.0f;
-            float la[4];
-            bool ok[4];
-            naqs::amp_conditional<true>(d, n, o, abits, bbits, la, ok);
-            const bool live = valid && (occ == 0 ? ok[0] : (occ == 1 ? ok[1] : (occ == 2 ? ok[2] : ok[3])));
-            float da4[4];
+            naqs::amp_block_delta(d, n, RAW, o, abits, bbits, occ, valid, valid ? g[i * g_stride] : 0.0f, dout);
 #pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const float sm = ok[c] ? expf(2.0f * la[c]) : 0.0f;
-                da4[c] = live && ok[c] ? gi * ((c == occ ? 1.0f : 0.0f) - sm) : 0.0f;
-            }
-            float dout[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            if (d.sym) {                                    // transpose of amp_symmetrise
-                const int x_order = abits > bbits ? 0 : (abits == bbits ? 1 : 2);
-                dout[0] = da4[0];
-                dout[2] = da4[3];
-                dout[1] = 0.5f * (da4[1] + da4[2]);
-                if (x_order == 1) dout[1] += 0.5f * (da4[1] + da4[2]);
-                else if (x_order == 0) { dout[3] = 0.5f * da4[1]; dout[4] = 0.5f * da4[2]; }
-                else { dout[4] = 0.5f * da4[1]; dout[3] = 0.5f * da4[2]; }
-            } else {
-                dout[0] = da4[0]; dout[1] = da4[1]; dout[2] = da4[2]; dout[3] = da4[3];
-            }
-#pragma unroll
-            for (int c = 0; c < 8; ++c) s_do[c * DGT + col] = dout[c];
-            const bool swap = d.sym && abits > bbits;
+            for (int c = 0; c < 8; ++c) s_do[c * DGT + col] = c < 5 ? dout[c] : 0.0f;
+            const bool swap = (RAW ? d.phase_sym : d.sym) && abits > bbits;
             s_x[col] = (swap ? bbits : abits) | ((swap ? abits : bbits) << 16);
         }
         __syncthreads();

@@ -34,7 +34,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 using naqs::ampbw::MAX_TILE_WGS;
 using naqs::ampbw::AmpSrc;
-using naqs::ampbw::GT;
+using naqs::ampbw::MAX_DYN_LDS;
 
 // out[i] = sum_n scratch[n][i] in the order of the fused log-psi epilogue
 __global__ __launch_bounds__(256) void logamp_sum_kernel(int P, int64_t M, const float *__restrict__ scratch,
@@ -337,23 +337,23 @@ int naqs::net_blocks_backward(naqs_net *net, const BlockSet &set, int64_t M, con
         HIP_TRY(hipMemsetAsync(grad_dev, 0, (size_t)set.n_params * sizeof(float), s));
         return NAQS_OK;
     }
-    const int n_wg = (int)std::min<int64_t>(MAX_TILE_WGS, (M + GT - 1) / GT);
+    const int n_wg = naqs::ampbw::tile_wgs(M);
     int64_t stride;
     float *gpart;
     int st = blocks_partials(net, slot, &stride, &gpart);
     if (st != NAQS_OK) return st;
     if (set.deep()) {
         const size_t lds_d = naqs::deep_bw_smem_floats(d.Ha, set.depth) * sizeof(float);
-        if (lds_d > 156 * 1024) return NAQS_ERR_UNSUPPORTED;
+        if (lds_d > MAX_DYN_LDS) return NAQS_ERR_UNSUPPORTED;
         const naqs::DeepAmp da = naqs::deep_blocks(set);
         st = naqs::dispatch_width(d.Ha >> 4, [&](auto c) -> int {
             constexpr int C = decltype(c)::value;
             if (set.raw) {                                  // deep phase blocks
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&amp_deep_backward_raw_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
+                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&amp_deep_backward_raw_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize, MAX_DYN_LDS));
                 NAQS_KLAUNCH(amp_deep_backward_raw_kernel<C>, dim3((unsigned)n_wg, (unsigned)d.P), dim3(naqs::DBW * WAVE), lds_d, s, d, set.w, da, M,
                              keys_dev, g_dev, 1, gpart, stride);
             } else {                                        // deep amplitude blocks
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&amp_deep_backward_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
+                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&amp_deep_backward_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize, MAX_DYN_LDS));
                 NAQS_KLAUNCH(amp_deep_backward_kernel<C>, dim3((unsigned)n_wg, (unsigned)d.P), dim3(naqs::DBW * WAVE), lds_d, s, d, set.w, da, M,
                              keys_dev, g_dev, gpart, stride);
             }
@@ -369,10 +369,9 @@ int naqs::net_blocks_backward(naqs_net *net, const BlockSet &set, int64_t M, con
     } else {
         const int NW = d.Ha >> 4;
         const size_t lds = naqs::ampbw::smem_floats(d) * sizeof(float);
-        if (lds > 156 * 1024) return NAQS_ERR_UNSUPPORTED;
+        if (lds > MAX_DYN_LDS) return NAQS_ERR_UNSUPPORTED;
         if (!net->grad_attr_set) {
-            const int lds_max = 156 * 1024;
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&amp_backward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&amp_backward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MAX_DYN_LDS));
             net->grad_attr_set = true;
         }
         NAQS_KLAUNCH(amp_backward_kernel, dim3((unsigned)n_wg, (unsigned)d.P), dim3((unsigned)(NW * WAVE)), lds, s, d, set.w, M, keys_dev,
@@ -399,7 +398,7 @@ int naqs::net_blocks_backward_plan(naqs_net *net, const BlockSet &set, int64_t M
     float *gpart;
     const int st = blocks_partials(net, slot, &stride, &gpart);
     if (st != NAQS_OK) return st;
-    job->count = set.n_params; job->stride = stride; job->n_partials = (int)std::min<int64_t>(MAX_TILE_WGS, (M + GT - 1) / GT);
+    job->count = set.n_params; job->stride = stride; job->n_partials = naqs::ampbw::tile_wgs(M);
     job->partial = gpart;
     *src = naqs::block_src<AmpSrc>(set, /*relative=*/true);
     return NAQS_OK;
@@ -413,7 +412,7 @@ int naqs::net_blocks_backward2(naqs_net *net, int64_t M, const uint64_t *keys_de
     if (d0.Ha != d1.Ha || d0.P != d1.P || M <= 0) return NAQS_ERR_INVALID;
     if (net->amp.deep()) {                        // deep blocks (naqs_net_create_agg_layers): agg_deep_backward_kernel, same partials
         if (d0.Ha > 128 || (d0.Ha & 15) || net->family != naqs::Family::AGGREGATE) return NAQS_ERR_UNSUPPORTED;
-        const int n_wg = (int)std::min<int64_t>(MAX_TILE_WGS, (M + GT - 1) / GT);
+        const int n_wg = naqs::ampbw::tile_wgs(M);
         const size_t lds_d = naqs::deep_bw_smem_floats(d0.Ha, net->amp.depth) * sizeof(float);
         jobs[0].count = net->amp.n_params; jobs[1].count = net->ph.n_params;
         for (int k = 0; k < 2; ++k) {
@@ -422,12 +421,12 @@ int naqs::net_blocks_backward2(naqs_net *net, int64_t M, const uint64_t *keys_de
             if (stp != NAQS_OK) return stp;
             jobs[k].n_partials = n_wg; jobs[k].partial = gpart;
         }
-        if (lds_d > 156 * 1024) return NAQS_ERR_UNSUPPORTED;
+        if (lds_d > MAX_DYN_LDS) return NAQS_ERR_UNSUPPORTED;
         const int64_t stride = jobs[0].stride;
         const naqs::DeepAmp da0 = naqs::deep_blocks(net->amp), da1 = naqs::deep_blocks(net->ph);
         const int st = naqs::dispatch_width(d0.Ha >> 4, [&](auto c) -> int {
             constexpr int C = decltype(c)::value;
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&agg_deep_backward_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&agg_deep_backward_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize, MAX_DYN_LDS));
             NAQS_KLAUNCH(agg_deep_backward_kernel<C>, dim3((unsigned)n_wg, (unsigned)d0.P, 2), dim3(naqs::DBW * WAVE), lds_d, s, d0, net->amp.w, da0,
                          const_cast<float *>(jobs[0].partial), d1, net->ph.w, da1, const_cast<float *>(jobs[1].partial), M, keys_dev, g_amp, g_ph,
                          g_stride, stride);
@@ -444,9 +443,9 @@ int naqs::net_blocks_backward2(naqs_net *net, int64_t M, const uint64_t *keys_de
     st = net_blocks_backward_plan(net, net->ph, M, 1, &jobs[1], &src1);
     if (st != NAQS_OK) return st;
     const size_t lds = std::max(naqs::ampbw::smem_floats(d0), naqs::ampbw::smem_floats(d1)) * sizeof(float);
-    if (lds > 156 * 1024) return NAQS_ERR_UNSUPPORTED;
+    if (lds > MAX_DYN_LDS) return NAQS_ERR_UNSUPPORTED;
     if (!net->grad2_attr_set) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&amp_backward2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&amp_backward2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MAX_DYN_LDS));
         net->grad2_attr_set = true;
     }
     NAQS_KLAUNCH(amp_backward2_kernel, dim3((unsigned)jobs[0].n_partials, (unsigned)d0.P, 2), dim3((unsigned)((d0.Ha >> 4) * WAVE)), lds, s,
@@ -465,13 +464,13 @@ int naqs::net_comb_backward(naqs_net *net, int64_t M, const uint64_t *keys_dev, 
         HIP_TRY(hipMemsetAsync(grad_dev, 0, (size_t)net->n_params * sizeof(float), s));
         return NAQS_OK;
     }
-    const int n_wg = (int)std::min<int64_t>(MAX_TILE_WGS, (M + GT - 1) / GT);
+    const int n_wg = naqs::ampbw::tile_wgs(M);
     const int64_t stride = (net->comb_amp + net->comb_head + 3) & ~3ll;
     if (!net->d_cpart) HIP_TRY(hipMalloc((void **)&net->d_cpart, (size_t)MAX_TILE_WGS * stride * sizeof(float)));
     const size_t lds = std::max(naqs::ampbw::smem_floats(d0), naqs::ampbw::smem_floats(d1)) * sizeof(float);
-    if (lds > 156 * 1024) return NAQS_ERR_UNSUPPORTED;
+    if (lds > MAX_DYN_LDS) return NAQS_ERR_UNSUPPORTED;
     if (!net->comb_attr_set) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&comb_backward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&comb_backward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MAX_DYN_LDS));
         net->comb_attr_set = true;
     }
     const AmpSrc src = naqs::block_src<AmpSrc>(net->amp, /*relative=*/true);

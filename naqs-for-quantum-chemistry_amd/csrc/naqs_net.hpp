@@ -188,6 +188,53 @@ __device__ __forceinline__ void amp_conditional(const NetDims &d, int NB, const 
     for (int c = 0; c < 4; ++c) la[c] = ok[c] ? 0.5f * ((a4[c] - m) - ls) : -INFINITY;
 }
 
+// what pair n's block sees of a key (the backward passes' decode): the alpha / beta strings of pairs 0 .. n - 1 and the realised
+// outcome occ = alpha + 2 beta of pair n itself
+struct PairView { uint32_t abits, bbits; int occ; };
+__device__ __forceinline__ PairView key_pair_view(const NetDims &d, const int n, const uint64_t key) {
+    PairView v{0u, 0u, 0};
+    for (int k = 0; k < n; ++k) {
+        v.abits |= (uint32_t)((key >> d.qa[k]) & 1ull) << k;
+        v.bbits |= (uint32_t)((key >> d.qb[k]) & 1ull) << k;
+    }
+    v.occ = (int)((key >> d.qa[n]) & 1ull) + 2 * (int)((key >> d.qb[n]) & 1ull);
+    return v;
+}
+
+// The block's output delta, the transpose of amp_conditional and amp_symmetrise: dout[c] = gi * d la[occ] / d o[c] from the
+// block's raw outputs o (0 for a sample that is not valid or whose outcome is masked).  raw (a phase block, whose realised
+// outcome's output is taken as it is): dout[c] = gi [c == phase_out_row(occ)], o is not read.
+__device__ __forceinline__ void amp_block_delta(const NetDims &d, const int NB, const bool raw, const float (&o)[5], const uint32_t abits,
+                                                const uint32_t bbits, const int occ, const bool valid, const float gi, float (&dout)[5]) {
+    if (raw) {
+#pragma unroll
+        for (int c = 0; c < 5; ++c) dout[c] = valid && c == phase_out_row(d, occ) ? gi : 0.0f;
+        return;
+    }
+    float la[4], da4[4];
+    bool ok[4];
+    amp_conditional<true>(d, NB, o, abits, bbits, la, ok);
+    // d la[occ] / d a4[c] = [c == occ] - softmax(2 a4)[c] on the allowed outcomes
+    const bool live = valid && (occ == 0 ? ok[0] : (occ == 1 ? ok[1] : (occ == 2 ? ok[2] : ok[3])));
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const float sm = ok[c] ? expf(2.0f * la[c]) : 0.0f;
+        da4[c] = live && ok[c] ? gi * ((c == occ ? 1.0f : 0.0f) - sm) : 0.0f;
+    }
+    dout[0] = dout[1] = dout[2] = dout[3] = dout[4] = 0.0f;
+    if (d.sym) {                                           // transpose of amp_symmetrise
+        const int x_order = abits > bbits ? 0 : (abits == bbits ? 1 : 2);
+        dout[0] = da4[0];
+        dout[2] = da4[3];
+        dout[1] = 0.5f * (da4[1] + da4[2]);
+        if (x_order == 1) dout[1] += 0.5f * (da4[1] + da4[2]);
+        else if (x_order == 0) { dout[3] = 0.5f * da4[1]; dout[4] = 0.5f * da4[2]; }
+        else { dout[4] = 0.5f * da4[1]; dout[3] = 0.5f * da4[2]; }
+    } else {
+        dout[0] = da4[0]; dout[1] = da4[1]; dout[2] = da4[2]; dout[3] = da4[3];
+    }
+}
+
 // ---- combined amplitude-phase blocks (Family::COMBINED) ----
 // The flat parameters are the state_dict's: blocks 0 .. P-2 as in a plain handle, then the last block
 // W1 [Ha][nin] | b1 [Ha] | W2 [na + nph][Ha] | b2 [na + nph] (amplitude rows first).  The kernels read two re-laid-out copies:

@@ -40,14 +40,11 @@ using naqs::NetDims;
 using naqs::DeviceGuard;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+using namespace naqs::bwtile;            // CH, LDD, pad64, up256 (naqs_sr.hpp)
 constexpr int TB = 64;       // output block edge
-constexpr int CH = 32;       // reduction chunk staged in LDS
 constexpr int LDT = 80;      // row stride of a [CH][64] tile: 80 = 16 mod 32 -> lanes (k, k+1) x 16 columns cover 32 banks
-constexpr int LDD = 34;      // row stride of a [64][CH] tile: bank = 2 row + k -> conflict-free for 16 rows x 2 k
 constexpr int W0_FUSE_MAX_ROWS = 4096;   // tables up to this size: the first layer's weight gradient is formed by the grad_in blocks
 constexpr int SUMS_FUSE_MAX_ROWS = 4096; // ... and the weighted sums of E_loc by the seed kernel's first workgroup (naqs_vmc_step)
-
-inline int pad64(int x) { return (x + 63) & ~63; }
 
 // delta of the output layer: only the realised outcome of the last pair carries the phase gradient
 __global__ __launch_bounds__(256) void top_delta_kernel(const NetDims d, const int64_t M, const uint64_t *__restrict__ keys,
@@ -642,8 +639,6 @@ struct TrainLayout {            // carve-up of net->d_train for `cap` rows
     int64_t cpart_floats;
 };
 
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 TrainLayout train_layout(const naqs_net *net, int64_t cap) {
     const NetDims &d = net->amp.d;
     TrainLayout L{};
@@ -696,6 +691,42 @@ size_t wb_offset(const naqs_net *net, int l) {
     size_t off = 0;
     for (int q = 0; q < l; ++q) off += (size_t)pad64(net->phase_N[(size_t)q]) * pad64(net->phase_K[(size_t)q]);
     return off;
+}
+
+// what the backward pass and the natural gradient need before they launch: the pending re-pack flushed (the row-major weight
+// copies they read belong to its phase share), the weights packed, and the training forward of the same batch behind them —
+// its scratch holds the M rows
+int backward_ready(naqs_net *net, const int64_t M, hipStream_t s) {
+    const int stj = naqs::net_flush_pack(net, s);
+    if (stj != NAQS_OK) return stj;
+    if (!net->have_weights || !net->have_wb) return NAQS_ERR_INVALID;
+    if (naqs::has_phase_mlp(net) && (M > net->train_cap || !net->d_train)) return NAQS_ERR_INVALID;
+    if (net->family == naqs::Family::AGGREGATE && M > 0 && (M > net->cap_M || !net->d_scratch)) return NAQS_ERR_INVALID;
+    return NAQS_OK;
+}
+
+// The unfused delta chain of the phase MLP in the training scratch, each launch written once: the output layer's delta from
+// the phase column of g [M][2] ...
+int launch_top_delta(const naqs_net *net, const TrainLayout &L, const int64_t M, const uint64_t *keys_dev, const float2 *g, hipStream_t s) {
+    float *top = reinterpret_cast<float *>(static_cast<char *>(net->d_train) + L.top);
+    NAQS_KLAUNCH(top_delta_kernel, dim3((unsigned)((M * L.top_ld + 255) / 256)), dim3(256), 0, s, net->amp.d, M, keys_dev, g, top, L.top_ld);
+    HIP_TRY(hipGetLastError());
+    return NAQS_OK;
+}
+// ... and the delta of layer l - 1's output from layer l's (dl) -> L.delta[l - 1]: below the output layer (l == H) one term per
+// element, no GEMM; grad_in_kernel otherwise
+int launch_layer_delta(const naqs_net *net, const TrainLayout &L, const int l, const float *dl, const int64_t M, const uint64_t *keys_dev,
+                       const float2 *g, hipStream_t s) {
+    char *base = static_cast<char *>(net->d_train);
+    const int Np = pad64(net->phase_N[(size_t)l]), Kp = pad64(net->phase_K[(size_t)l]);
+    const float *in = reinterpret_cast<const float *>(base + L.act[l - 1]), *W = net->d_wb + wb_offset(net, l);
+    float *dnext = reinterpret_cast<float *>(base + L.delta[l - 1]);
+    if (l == net->amp.d.n_lin - 1)
+        NAQS_KLAUNCH(delta_below_top_kernel, dim3((unsigned)((M * (Kp >> 2) + 255) / 256)), dim3(256), 0, s, net->amp.d, M, keys_dev, g, W, in, Kp, dnext);
+    else
+        NAQS_KLAUNCH(grad_in_kernel, dim3((unsigned)((M + TB - 1) / TB), Kp / TB), dim3(256), 0, s, dl, W, in, M, Np, Kp, dnext);
+    HIP_TRY(hipGetLastError());
+    return NAQS_OK;
 }
 
 }  // namespace
@@ -872,16 +903,12 @@ static int launch_grad_finish(const GradFinish &F, const GradWJobs &J, const flo
 static int train_backward_impl(naqs_net_t *net, int64_t M, const uint64_t *keys_dev, const float *g_dev, float *grad_dev, void *stream,
                                const VmcSeeds *seeds, const naqs::AdamArgs *adam = nullptr) {
     if (!net || M < 0 || !grad_dev || (M > 0 && (!keys_dev || !g_dev))) return NAQS_ERR_INVALID;
-    {   // (the row-major weight copies this pass reads belong to the phase share of the re-pack)
-        const int stj = naqs::net_flush_pack(net, reinterpret_cast<hipStream_t>(stream));
-        if (stj != NAQS_OK) return stj;
-    }
-    if (!net->have_weights || !net->have_wb) return NAQS_ERR_INVALID;
-    if (naqs::has_phase_mlp(net) && (M > net->train_cap || !net->d_train)) return NAQS_ERR_INVALID;   // naqs_net_train_forward of the same batch comes first
-    DeviceGuard guard;
-    int st = guard.init(net->device);
-    if (st != NAQS_OK) return st;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    int st = backward_ready(net, M, s);
+    if (st != NAQS_OK) return st;
+    DeviceGuard guard;
+    st = guard.init(net->device);
+    if (st != NAQS_OK) return st;
     if (M == 0) {
         if (adam) return NAQS_ERR_INVALID;
         HIP_TRY(hipMemsetAsync(grad_dev, 0, (size_t)net->n_params * sizeof(float), s));
@@ -895,7 +922,6 @@ static int train_backward_impl(naqs_net_t *net, int64_t M, const uint64_t *keys_
         // both sets of per-pair blocks through the same backward kernel: amplitude blocks on g[:, 0], phase blocks (raw
         // outputs, no conditional) on g[:, 1]; the forward scratch ([2 P][cap] floats, free by now) holds the two columns.
         // (deep blocks, naqs_net_create_agg_layers: the same two forms on the deep kernels — naqs_grad.hip)
-        if (M > net->cap_M || !net->d_scratch) return NAQS_ERR_INVALID;
         if (net->amp.d.Ha == net->ph.d.Ha && net->amp.d.P == net->ph.d.P && (naqs::env_int("NAQS_AGG_MERGE", 7) & 2)) {
             // one launch for both sets, the two columns of g read where they are
             st = naqs::net_blocks_backward2(net, M, keys_dev, g_dev, g_dev + 1, 2, F.set, s);
@@ -968,8 +994,8 @@ static int train_backward_impl(naqs_net_t *net, int64_t M, const uint64_t *keys_
 
     // phase block.  First the chain of deltas, output layer down (the critical path: each needs the one above) ...
     if (seeds == nullptr) {
-        NAQS_KLAUNCH(top_delta_kernel, dim3((unsigned)((M * L.top_ld + 255) / 256)), dim3(256), 0, s, d, M, keys_dev, g2, top, L.top_ld);
-        HIP_TRY(hipGetLastError());
+        st = launch_top_delta(net, L, M, keys_dev, g2, s);
+        if (st != NAQS_OK) return st;
     }
     const float *dl[MAXL];                            // delta of linear layer l's output
     dl[H] = top;
@@ -983,30 +1009,20 @@ static int train_backward_impl(naqs_net_t *net, int64_t M, const uint64_t *keys_
                                                        : ((M + 31) / 32 * (pad64(net->phase_K[(size_t)(H >= 1 ? 1 : 0)]) / TB) <= 4ll * net->cu_count ? 32 : 64);
     const bool w0_tiles = H == 2 && d.Ha == 64 && M <= W0_FUSE_MAX_ROWS && pad64(net->phase_K[0]) == TB;
     for (int l = H; l > 0; --l) {
-        const int Np = pad64(net->phase_N[(size_t)l]), Kp = pad64(net->phase_K[(size_t)l]);
-        const float *in = reinterpret_cast<const float *>(base + L.act[l - 1]);
         float *dnext = reinterpret_cast<float *>(base + L.delta[l - 1]);
-        if (l == H && seed_delta) { dl[l - 1] = dnext; continue; }
-        if (l == H) {                                     // below the output layer: one term per element, no GEMM
-            const float2 *gsrc = seeds != nullptr ? reinterpret_cast<const float2 *>(seeds->g_out) : g2;
-            NAQS_KLAUNCH(delta_below_top_kernel, dim3((unsigned)((M * (Kp >> 2) + 255) / 256)), dim3(256), 0, s, d, M, keys_dev, gsrc,
-                               net->d_wb + wb_offset(net, l), in, Kp, dnext);
-            HIP_TRY(hipGetLastError());
-            dl[l - 1] = dnext;
-            continue;
-        }
-        if (mega) {                                       // (l == 1 here: part of the one launch below)
+        dl[l - 1] = dnext;
+        if (l == H && seed_delta) continue;               // (vmc_seed_delta_kernel has written it)
+        if (mega && l < H) {                              // (l == 1 here: part of the one launch below)
+            const int Np = pad64(net->phase_N[(size_t)l]), Kp = pad64(net->phase_K[(size_t)l]);
             A.gin_tbm = gin_tbm;
             A.gin_tiles_i = (int)((M + A.gin_tbm - 1) / A.gin_tbm);
             A.n_gin = A.gin_tiles_i * (Kp / TB);
-            A.D = dl[l]; A.W = net->d_wb + wb_offset(net, l); A.In = in; A.Dout = dnext; A.Np = Np; A.Kp = Kp;
-            dl[l - 1] = dnext;
+            A.D = dl[l]; A.W = net->d_wb + wb_offset(net, l); A.In = reinterpret_cast<const float *>(base + L.act[l - 1]);
+            A.Dout = dnext; A.Np = Np; A.Kp = Kp;
             continue;
         }
-        NAQS_KLAUNCH(grad_in_kernel, dim3((unsigned)((M + TB - 1) / TB), Kp / TB), dim3(256), 0, s, dl[l],
-                           net->d_wb + wb_offset(net, l), in, M, Np, Kp, dnext);
-        HIP_TRY(hipGetLastError());
-        dl[l - 1] = dnext;
+        st = launch_layer_delta(net, L, l, dl[l], M, keys_dev, seeds != nullptr ? reinterpret_cast<const float2 *>(seeds->g_out) : g2, s);
+        if (st != NAQS_OK) return st;
     }
     // ... then every layer's weight gradient in one launch and one fixed-order reduction
     GradWJobs J{};
@@ -1326,44 +1342,26 @@ NAQS_API int naqs_net_train_backward_vmc(naqs_net_t *net, int64_t M, const uint6
 }
 
 // ---- natural-gradient training (naqs_sr.hip): the phase MLP's per-sample factors, host sequencing only ----
-int naqs::net_sr_begin(naqs_net *net, int64_t M, hipStream_t s) {
-    const int stj = naqs::net_flush_pack(net, s);
-    if (stj != NAQS_OK) return stj;
-    if (!net->have_weights || !net->have_wb) return NAQS_ERR_INVALID;
-    if (naqs::has_phase_mlp(net) && (M > net->train_cap || !net->d_train)) return NAQS_ERR_INVALID;   // no training forward held
-    if (!naqs::has_phase_mlp(net) && (M > net->cap_M || !net->d_scratch)) return NAQS_ERR_INVALID;
-    return NAQS_OK;
-}
+int naqs::net_sr_begin(naqs_net *net, int64_t M, hipStream_t s) { return backward_ready(net, M, s); }
 
 // The deltas of every phase layer for the seeds unit_g = (., 1): d phase_i / d (layer l's output), left in the training
-// scratch where the unfused backward leaves them (leading dimension pad64(N_l)); the layer's input is the saved x or the
-// activation below.  Same kernels, same launch shapes as train_backward_impl's unfused chain.
+// scratch by the backward pass's own unfused chain (leading dimension pad64(N_l)); the layer's input is the saved x or the
+// activation below.
 int naqs::net_sr_phase_factors(naqs_net *net, int64_t M, const uint64_t *keys_dev, const float *unit_g, naqs::SrJobs *jobs,
                                hipStream_t s) {
     if (!naqs::has_phase_mlp(net) || M <= 0 || M > net->train_cap || !net->d_train || !net->have_wb || !jobs) return NAQS_ERR_INVALID;
-    const NetDims &d = net->amp.d;
     const TrainLayout L = train_layout(net, net->train_cap);
     char *base = static_cast<char *>(net->d_train);
-    float *top = reinterpret_cast<float *>(base + L.top);
     const float2 *g2 = reinterpret_cast<const float2 *>(unit_g);
-    const int H = d.n_lin - 1;
-    NAQS_KLAUNCH(top_delta_kernel, dim3((unsigned)((M * L.top_ld + 255) / 256)), dim3(256), 0, s, d, M, keys_dev, g2, top, L.top_ld);
-    HIP_TRY(hipGetLastError());
+    const int H = net->amp.d.n_lin - 1;
+    int st = launch_top_delta(net, L, M, keys_dev, g2, s);
+    if (st != NAQS_OK) return st;
     const float *dl[MAXL];
-    dl[H] = top;
+    dl[H] = reinterpret_cast<const float *>(base + L.top);
     for (int l = H; l > 0; --l) {
-        const int Np = pad64(net->phase_N[(size_t)l]), Kp = pad64(net->phase_K[(size_t)l]);
-        const float *in = reinterpret_cast<const float *>(base + L.act[l - 1]);
-        float *dnext = reinterpret_cast<float *>(base + L.delta[l - 1]);
-        if (l == H) {
-            NAQS_KLAUNCH(delta_below_top_kernel, dim3((unsigned)((M * (Kp >> 2) + 255) / 256)), dim3(256), 0, s, d, M, keys_dev, g2,
-                               net->d_wb + wb_offset(net, l), in, Kp, dnext);
-        } else {
-            NAQS_KLAUNCH(grad_in_kernel, dim3((unsigned)((M + TB - 1) / TB), Kp / TB), dim3(256), 0, s, dl[l],
-                               net->d_wb + wb_offset(net, l), in, M, Np, Kp, dnext);
-        }
-        HIP_TRY(hipGetLastError());
-        dl[l - 1] = dnext;
+        st = launch_layer_delta(net, L, l, dl[l], M, keys_dev, g2, s);
+        if (st != NAQS_OK) return st;
+        dl[l - 1] = reinterpret_cast<const float *>(base + L.delta[l - 1]);
     }
     jobs->n = H + 1;
     for (int l = 0; l <= H; ++l) {

@@ -12,8 +12,9 @@
 // sample's gradient for it is delta_i (x) a_i, and the layer adds (Delta Delta^T) o (A A^T + 1) to the uncentred Gram matrix
 // G = A A^T — two thin GEMMs over the sample axis and one elementwise product per layer.
 //
-//   sr_amp_factors_kernel  stage (1) of amp_backward_pair (naqs_amp_backward.hpp) with unit seeds: per pair and sample the
-//                          block's inputs x (the bias as an explicit column of ones), hidden activations h, d-pre and d-out
+//   sr_amp_factors_kernel  the backward pass's stage (1) (naqs_amp_backward.hpp: stage1_tile) on unit seeds, the tile written out
+//                          instead of contracted: per pair and sample the block's inputs x (the bias as an explicit column of
+//                          ones), hidden activations h, d-pre and d-out
 //   sr_gram_kernel         one workgroup per 64 x 64 tile (I, J >= I): per factor pair both products of the float32 factors on
 //                          v_mfma_f64_16x16x4_f64 (exact products, float64 sums), multiplied elementwise and accumulated in
 //                          float64 in a fixed order.  G is then EXACTLY the Gram matrix of the float32 factors: T is positive
@@ -42,143 +43,38 @@ using naqs::SrJobs;
 using naqs::WAVE;
 using naqs::DeviceGuard;
 using naqs::ampbw::GT;
-using naqs::ampbw::MAX_TILE_WGS;
+using naqs::ampbw::LD;
+using naqs::ampbw::MAX_DYN_LDS;
+using namespace naqs::bwtile;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TB = 64;       // Gram tile edge
-constexpr int CH = 32;       // feature chunk staged in LDS
-constexpr int LDD = 34;      // row stride of a [64][CH] tile (naqs_phase_grad.hip: conflict-free for 16 rows x 2 k)
 constexpr int XLD = 64;      // leading dimension of the x and d-out factors; CH of their columns are written and read
-
-inline int pad64(int x) { return (x + 63) & ~63; }
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // where pair n's factors of one block set go: [pair][cap rows][ld]
 struct SrFactorOut { float *x, *dout, *h, *dh; int64_t cap; int ldh; };
 
-// One orbital pair NB, all tiles of this workgroup: amp_backward_pair's stage (1) — same forward, same d-out, same d-pre, wave
-// q owning hidden units 16 q .. 16 q + 15 — with the seed 1 for every valid sample, and the tile written out instead of
-// contracted.  smem as there: weights | d-pre tile [Ha][65] | h tile [Ha][65] | d-out [5][64] | input bits [64] | partial
-// outputs [Ha/16][5][64].  raw: the phase blocks of an aggregate-phase network.
+// One orbital pair NB, all tiles of this workgroup: the backward pass's stage (1) on the seeds g (stride 2; the caller's are all
+// 1), the tile it leaves in LDS written out as the pair's factors.  raw: the phase blocks of an aggregate-phase network.
 template <int NB>
 __device__ __forceinline__ void sr_factors_pair(const NetDims &d, const float *__restrict__ w, const int64_t M,
-                                                const uint64_t *__restrict__ keys, const SrFactorOut &F, float *smem, const int raw,
-                                                const int wg, const int n_wgs) {
+                                                const uint64_t *__restrict__ keys, const float *__restrict__ g, const SrFactorOut &F,
+                                                float *smem, const int raw, const int wg, const int n_wgs) {
     constexpr int NIN = NB == 0 ? 1 : 2 * NB;
-    constexpr int S = naqs::amp_row_stride(NIN);
-    constexpr int LD = GT + 1;
     static_assert(NIN + 1 <= CH, "the inputs and the bias fit one chunk of columns");
-    const int Ha = d.Ha, nout = d.n_out_amp, NW = Ha >> 4, NT = NW * WAVE;
-    const int w_floats = (Ha * S + 8 + 3) & ~3;
-    float *s_w = smem;
-    float *s_dpre = s_w + w_floats;
-    float *s_h = s_dpre + Ha * LD;
-    float *s_do = s_h + Ha * LD;                          // [5][GT]
-    uint32_t *s_x = reinterpret_cast<uint32_t *>(s_do + 5 * GT);
-    float *s_part = reinterpret_cast<float *>(s_x + GT);  // [NW][5][GT]
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    {
-        const f32x4 *from = reinterpret_cast<const f32x4 *>(w + d.amp_off[NB]);
-        f32x4 *to = reinterpret_cast<f32x4 *>(s_w);
-        for (int e = tid; e < (Ha * S + 8) / 4; e += NT) to[e] = from[e];
-    }
-    const float *b2 = s_w + Ha * S;
-    const int j0 = wave * 16;
+    const int Ha = d.Ha, NT = (Ha >> 4) * WAVE, tid = threadIdx.x;
+    const naqs::ampbw::TileLds T = naqs::ampbw::tile_lds(Ha, naqs::amp_row_stride(NIN));
+    const float *s_dpre = smem + T.dpre, *s_h = smem + T.h, *s_do = smem + T.dout;
+    const uint32_t *s_x = reinterpret_cast<const uint32_t *>(smem + T.x);
+    naqs::ampbw::stage_weights<NB>(d, w, smem);
     float *xo = F.x + (int64_t)NB * F.cap * XLD, *doo = F.dout + (int64_t)NB * F.cap * XLD;
     float *ho = F.h + (int64_t)NB * F.cap * F.ldh, *dho = F.dh + (int64_t)NB * F.cap * F.ldh;
     __syncthreads();
 
     for (int64_t t0 = (int64_t)wg * GT; t0 < M; t0 += (int64_t)n_wgs * GT) {
-        const int64_t i = t0 + lane;
-        const bool valid = i < M;
-        const uint64_t key = valid ? keys[i] : 0ull;
-        uint32_t abits = 0, bbits = 0;
-#pragma unroll
-        for (int k = 0; k < NB; ++k) {
-            abits |= (uint32_t)((key >> d.qa[k]) & 1ull) << k;
-            bbits |= (uint32_t)((key >> d.qb[k]) & 1ull) << k;
-        }
-        const int occ = (int)((key >> d.qa[NB]) & 1ull) + 2 * (int)((key >> d.qb[NB]) & 1ull);
-        const bool swap = (raw ? d.phase_sym != 0 : d.sym != 0) && abits > bbits;
-        const uint32_t first = swap ? bbits : abits, second = swap ? abits : bbits;
-        float x[NIN];
-        if (NB == 0) {
-            x[0] = 0.0f;
-        } else {
-#pragma unroll
-            for (int k = 0; k < NB; ++k) {
-                x[k] = ((first >> k) & 1u) ? 1.0f : -1.0f;
-                x[NB + k] = ((second >> k) & 1u) ? 1.0f : -1.0f;
-            }
-        }
-        const float gi = valid ? 1.0f : 0.0f;
-        float o[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll 2
-        for (int jj = j0; jj < j0 + 16; ++jj) {
-            float rv[S];
-            naqs::load_row<S>(s_w + jj * S, rv);
-            float h0 = rv[NIN], h1 = 0.0f;
-#pragma unroll
-            for (int k = 0; k + 1 < NIN; k += 2) { h0 = fmaf(rv[k], x[k], h0); h1 = fmaf(rv[k + 1], x[k + 1], h1); }
-            if (NIN & 1) h0 = fmaf(rv[NIN - 1], x[NIN - 1], h0);
-            const float h = fmaxf(h0 + h1, 0.0f);
-            s_h[jj * LD + lane] = h;
-#pragma unroll
-            for (int c = 0; c < 5; ++c)
-                if (c < nout) o[c] = fmaf(rv[NIN + 1 + c], h, o[c]);
-        }
-#pragma unroll
-        for (int c = 0; c < 5; ++c) s_part[(wave * 5 + c) * GT + lane] = o[c];
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < 5; ++c) {
-            float v = c < nout ? b2[c] : 0.0f;
-            for (int q = 0; q < NW; ++q) v += s_part[(q * 5 + c) * GT + lane];
-            o[c] = v;
-        }
-        float da4[4];
-        if (raw) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) da4[c] = valid && c == naqs::phase_out_row(d, occ) ? gi : 0.0f;
-        } else {
-            float la[4];
-            bool ok[4];
-            naqs::amp_conditional<true>(d, NB, o, abits, bbits, la, ok);
-            const bool live = valid && (occ == 0 ? ok[0] : (occ == 1 ? ok[1] : (occ == 2 ? ok[2] : ok[3])));
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const float sm = ok[c] ? expf(2.0f * la[c]) : 0.0f;
-                da4[c] = live && ok[c] ? gi * ((c == occ ? 1.0f : 0.0f) - sm) : 0.0f;
-            }
-        }
-        float dout[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-        if (d.sym) {                                       // transpose of amp_symmetrise
-            const int x_order = abits > bbits ? 0 : (abits == bbits ? 1 : 2);
-            dout[0] = da4[0];
-            dout[2] = da4[3];
-            dout[1] = 0.5f * (da4[1] + da4[2]);
-            if (x_order == 1) dout[1] += 0.5f * (da4[1] + da4[2]);
-            else if (x_order == 0) { dout[3] = 0.5f * da4[1]; dout[4] = 0.5f * da4[2]; }
-            else { dout[4] = 0.5f * da4[1]; dout[3] = 0.5f * da4[2]; }
-        } else {
-            dout[0] = da4[0]; dout[1] = da4[1]; dout[2] = da4[2]; dout[3] = da4[3];
-        }
-        if (wave == 0) {
-#pragma unroll
-            for (int c = 0; c < 5; ++c) s_do[c * GT + lane] = dout[c];
-            s_x[lane] = (NB == 0 ? 0u : (first | (second << NB))) | (1u << NIN);   // bit NIN: the bias input
-        }
-#pragma unroll 4
-        for (int jj = j0; jj < j0 + 16; ++jj) {
-            const float *row = s_w + jj * S + NIN + 1;
-            float dh = 0.0f;
-#pragma unroll
-            for (int c = 0; c < 5; ++c)
-                if (c < nout) dh = fmaf(row[c], dout[c], dh);
-            s_dpre[jj * LD + lane] = s_h[jj * LD + lane] > 0.0f ? dh : 0.0f;
-        }
-        __syncthreads();
+        float dout[5];
+        naqs::ampbw::stage1_tile<NB>(d, smem, M, keys, g, 2, raw, t0, dout);
         // the tile's factors, row-major: consecutive threads take consecutive columns of a sample's row
         for (int e = tid; e < GT * Ha; e += NT) {
             const int r = e / Ha, j = e - r * Ha;
@@ -204,16 +100,12 @@ __device__ __forceinline__ void sr_factors_pair(const NetDims &d, const float *_
 
 // amp_backward_kernel's launch shape: workgroup = pair blockIdx.y x a strided set of 64-sample tiles, Ha / 16 waves
 __global__ __launch_bounds__(512) void sr_amp_factors_kernel(const NetDims d, const float *__restrict__ w, const int64_t M,
-                                                             const uint64_t *__restrict__ keys, const SrFactorOut F, const int raw) {
+                                                             const uint64_t *__restrict__ keys, const float *__restrict__ g,
+                                                             const SrFactorOut F, const int raw) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int wg = (int)blockIdx.x, n_wgs = (int)gridDim.x;
-    switch ((int)blockIdx.y) {
-#define NAQS_CASE(NB) case NB: sr_factors_pair<NB>(d, w, M, keys, F, smem, raw, wg, n_wgs); break;
-        NAQS_CASE(0) NAQS_CASE(1) NAQS_CASE(2) NAQS_CASE(3) NAQS_CASE(4) NAQS_CASE(5) NAQS_CASE(6) NAQS_CASE(7)
-        NAQS_CASE(8) NAQS_CASE(9) NAQS_CASE(10) NAQS_CASE(11) NAQS_CASE(12) NAQS_CASE(13) NAQS_CASE(14) NAQS_CASE(15)
-#undef NAQS_CASE
-        default: break;
-    }
+    naqs::ampbw::for_pair((int)blockIdx.y, [&](auto nb) {
+        sr_factors_pair<decltype(nb)::value>(d, w, M, keys, g, F, smem, raw, (int)blockIdx.x, (int)gridDim.x);
+    });
 }
 
 // acc[a][b] += F[I rows][0..K) . F[J rows][0..K)^T for this wave's 32 x 32 sub-block (2 x 2 MFMA tiles): 32-deep chunks of both
@@ -441,16 +333,15 @@ int sr_block_factors(naqs_net *net, const naqs::BlockSet &set, const int k, cons
     const NetDims &d = set.d;
     if (d.Ha > 128 || (d.Ha & 15) || set.deep() || 2 * d.P > naqs::SR_MAX_JOBS) return NAQS_ERR_UNSUPPORTED;
     const size_t lds = naqs::ampbw::smem_floats(d) * sizeof(float);
-    if (lds > 156 * 1024) return NAQS_ERR_UNSUPPORTED;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&sr_amp_factors_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
+    if (lds > MAX_DYN_LDS) return NAQS_ERR_UNSUPPORTED;
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&sr_amp_factors_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MAX_DYN_LDS));
     char *base = static_cast<char *>(net->d_sr);
     SrFactorOut F;
     F.x = reinterpret_cast<float *>(base + L.x[k]); F.dout = reinterpret_cast<float *>(base + L.dout[k]);
     F.h = reinterpret_cast<float *>(base + L.h[k]); F.dh = reinterpret_cast<float *>(base + L.dh[k]);
     F.cap = net->sr_cap; F.ldh = L.ldh[k];
-    const int n_wg = (int)std::min<int64_t>(MAX_TILE_WGS, (M + GT - 1) / GT);
-    NAQS_KLAUNCH(sr_amp_factors_kernel, dim3((unsigned)n_wg, (unsigned)d.P), dim3((unsigned)((d.Ha >> 4) * WAVE)), lds, s, d, set.w, M,
-                       keys_dev, F, set.raw ? 1 : 0);
+    NAQS_KLAUNCH(sr_amp_factors_kernel, dim3((unsigned)naqs::ampbw::tile_wgs(M), (unsigned)d.P), dim3((unsigned)((d.Ha >> 4) * WAVE)), lds, s,
+                       d, set.w, M, keys_dev, reinterpret_cast<const float *>(base + L.unit), F, set.raw ? 1 : 0);
     HIP_TRY(hipGetLastError());
     jobs->n = 2 * d.P;
     const int kh = (d.Ha + 31) & ~31;

@@ -1,5 +1,5 @@
 // naqs_sr.hpp — what the natural-gradient (minSR) entry points of naqs_sr.hip share with the training backward
-// (naqs_phase_grad.hip): the factor pairs the Gram kernel walks, and the host sequencing of the phase MLP's delta chain.
+// (naqs_phase_grad.hip): the geometry of the GEMM tiles, the factor pairs the Gram kernel walks, and the phase MLP's delta chain.
 #pragma once
 #include <cstdint>
 
@@ -7,6 +7,15 @@
 #include "naqs_net.hpp"
 
 namespace naqs {
+
+// the LDS operand tile of the sample-axis GEMMs (grad_w_kernel, grad_in_kernel, sr_gram_kernel) and the padding of their operands
+// (each kernel's block edge TB stays with the kernel: the test suite reads the backward pass's from naqs_phase_grad.hip)
+namespace bwtile {
+constexpr int CH = 32;       // reduction chunk staged in LDS
+constexpr int LDD = 34;      // row stride of a [64][CH] tile: bank = 2 row + k -> conflict-free for 16 rows x 2 k
+inline int pad64(int x) { return (x + 63) & ~63; }
+inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+}  // namespace bwtile
 
 // A Linear layer's per-sample gradient is delta_i (x) a_i, so the layer adds (D D^T) o (A A^T + 1) to the M x M Gram
 // matrix of the per-sample gradients (`one`: the bias is not a column of A).  Factor l: D_l [M][ldd] and A_l [M][lda],
@@ -19,10 +28,9 @@ struct SrJobs {
 };
 constexpr int SR_MAX_ROWS = 32768;       // the Gram matrices are O(M^2) doubles: 8.6 GB each at this size
 
-// naqs_phase_grad.hip.  net_sr_begin: what naqs_net_train_backward checks before it launches (pending re-pack flushed, weights
-// packed, the training forward's scratch holds M rows).  net_sr_phase_factors: the unfused delta chain of the single phase MLP
-// (top_delta_kernel -> delta_below_top_kernel -> grad_in_kernel) with the seeds unit_g [M][2] = (., 1), into the training
-// scratch; the layers' (delta, input) pairs -> jobs.
+// naqs_phase_grad.hip.  net_sr_begin: naqs_net_train_backward's own readiness check (pending re-pack flushed, weights packed, the
+// training forward's scratch holds M rows).  net_sr_phase_factors: the training backward's delta chain of the single phase MLP
+// (phase_delta_chain) with the seeds unit_g [M][2] = (., 1), into the training scratch; the layers' (delta, input) pairs -> jobs.
 int net_sr_begin(naqs_net *net, int64_t M, hipStream_t s);
 int net_sr_phase_factors(naqs_net *net, int64_t M, const uint64_t *keys_dev, const float *unit_g, SrJobs *jobs, hipStream_t s);
 
