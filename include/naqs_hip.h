@@ -445,6 +445,16 @@ int naqs_net_sr_gram(naqs_net_t *net, int64_t M, const uint64_t *keys_dev, const
 int naqs_net_sr_gram_uncentred(naqs_net_t *net, int64_t M, const uint64_t *keys_dev, double *Ga_dev, double *Gphi_dev, void *stream);
 int naqs_net_sr_direction(naqs_net_t *net, int64_t M, const uint64_t *keys_dev, const double *w_dev, const double *xa_dev,
                           const double *xphi_dev, float *dir_dev, void *stream);
+/* The Jacobian-vector products of the same table: ua_dev [M] = A v and uphi_dev [M] = B v (float64, uncentred) for a vector
+ * v_dev [naqs_net_param_count] float32 in state_dict order — the operand X phi_prev of a momentum step (SPRING: Goldshlager,
+ * Abrahamsen, Lin 2024), centred by the caller as u - w^T u.  No Jacobian is formed: with layer l's per-sample factors
+ * (delta_l,i, a_l,i) of naqs_net_sr_gram, (J v)_i = sum_l delta_l,i^T (V_l a_l,i + v_b,l), V_l and v_b,l the slices of v that are
+ * the layer's weight and bias, read in place; float32 factors (the per-pair blocks' from a float64 evaluation, rounded once: the
+ * training stage's d-out and d-pre are cancelling float32 sums) and v, exact products and float64 sums in a fixed order:
+ * deterministic, and u_i depends on row i alone (the same bits at any M that holds the row).  The factors are recomputed by
+ * every call.  Handles, preconditions and status codes as naqs_net_sr_gram_uncentred; a null pointer -> NAQS_ERR_INVALID. */
+int naqs_net_sr_jvp(naqs_net_t *net, int64_t M, const uint64_t *keys_dev, const float *v_dev, double *ua_dev, double *uphi_dev,
+                    void *stream);
 /* The solves between naqs_net_sr_gram and naqs_net_sr_direction: T x = y for the one or two symmetric positive definite [M][M]
  * row-major float64 matrices that naqs_net_sr_gram wrote, by a blocked Cholesky factorisation T = L L^T (64-wide block columns,
  * the trailing updates on the float64 matrix cores) and the forward and back substitutions, all in float64 — what

@@ -1348,7 +1348,7 @@ int naqs::net_sr_begin(naqs_net *net, int64_t M, hipStream_t s) { return backwar
 // scratch by the backward pass's own unfused chain (leading dimension pad64(N_l)); the layer's input is the saved x or the
 // activation below.
 int naqs::net_sr_phase_factors(naqs_net *net, int64_t M, const uint64_t *keys_dev, const float *unit_g, naqs::SrJobs *jobs,
-                               hipStream_t s) {
+                               hipStream_t s, naqs::SrJvpMap *map) {
     if (!naqs::has_phase_mlp(net) || M <= 0 || M > net->train_cap || !net->d_train || !net->have_wb || !jobs) return NAQS_ERR_INVALID;
     const TrainLayout L = train_layout(net, net->train_cap);
     char *base = static_cast<char *>(net->d_train);
@@ -1371,6 +1371,10 @@ int naqs::net_sr_phase_factors(naqs_net *net, int64_t M, const uint64_t *keys_de
         jobs->lda[l] = l == 0 ? L.x_ld : L.act_ld[l - 1];
         jobs->ka[l] = (K + 31) & ~31;
         jobs->one[l] = 1;
+        if (map) {                                        // W [N][K] then b [N], where the backward writes their gradients
+            map->w[l] = net->phase_src_off[(size_t)l]; map->b[l] = map->w[l] + (int64_t)N * K;
+            map->ld[l] = K; map->rows[l] = N; map->cols[l] = K;
+        }
     }
     return NAQS_OK;
 }

@@ -8,7 +8,7 @@
 
 namespace naqs {
 
-// the LDS operand tile of the sample-axis GEMMs (grad_w_kernel, grad_in_kernel, sr_gram_kernel) and the padding of their operands
+// the LDS operand tile of the sample-axis GEMMs (grad_w_kernel, grad_in_kernel, sr_gram_kernel, sr_jvp_kernel) and the padding of their operands
 // (each kernel's block edge TB stays with the kernel: the test suite reads the backward pass's from naqs_phase_grad.hip)
 namespace bwtile {
 constexpr int CH = 32;       // reduction chunk staged in LDS
@@ -26,12 +26,22 @@ struct SrJobs {
     const float *D[SR_MAX_JOBS], *A[SR_MAX_JOBS];
     int ldd[SR_MAX_JOBS], lda[SR_MAX_JOBS], kd[SR_MAX_JOBS], ka[SR_MAX_JOBS], one[SR_MAX_JOBS];
 };
+// Where job l's Linear layer sits in a flat parameter-shaped vector v (state_dict order), for the Jacobian-vector product
+// (sr_jvp_kernel): the weight V_l = v[w ...] as [rows][cols] with row stride ld (unpadded), the bias v_b = v[b ...] as [rows].
+// rows is the true width of D_l, cols the true width of A_l; a job with one = 0 has the bias as column `cols` of V_l (where its A
+// factor holds the ones).  Filled beside SrJobs, which stays as sr_gram_kernel takes it.
+struct SrJvpMap {
+    int64_t w[SR_MAX_JOBS], b[SR_MAX_JOBS];
+    int ld[SR_MAX_JOBS], rows[SR_MAX_JOBS], cols[SR_MAX_JOBS];
+};
 constexpr int SR_MAX_ROWS = 32768;       // the Gram matrices are O(M^2) doubles: 8.6 GB each at this size
 
 // naqs_phase_grad.hip.  net_sr_begin: naqs_net_train_backward's own readiness check (pending re-pack flushed, weights packed, the
 // training forward's scratch holds M rows).  net_sr_phase_factors: the training backward's delta chain of the single phase MLP
-// (phase_delta_chain) with the seeds unit_g [M][2] = (., 1), into the training scratch; the layers' (delta, input) pairs -> jobs.
+// (phase_delta_chain) with the seeds unit_g [M][2] = (., 1), into the training scratch; the layers' (delta, input) pairs -> jobs,
+// and with `map` where each layer's weight and bias sit in the flat parameters.
 int net_sr_begin(naqs_net *net, int64_t M, hipStream_t s);
-int net_sr_phase_factors(naqs_net *net, int64_t M, const uint64_t *keys_dev, const float *unit_g, SrJobs *jobs, hipStream_t s);
+int net_sr_phase_factors(naqs_net *net, int64_t M, const uint64_t *keys_dev, const float *unit_g, SrJobs *jobs, hipStream_t s,
+                         SrJvpMap *map = nullptr);
 
 }  // namespace naqs

@@ -55,6 +55,7 @@ _VALUE_FLAGS = [
     (("-sr_lr",), "sr_lr", dict(type=float, help="Natural gradient: learning rate.")),
     (("-sr_solver",), "sr_solver", dict(type=str, choices=["torch", "hip"],
                                         help="Natural gradient: the two Cholesky solves by torch (the default) or by naqs_net_sr_solve.")),
+    (("-sr_momentum",), "sr_momentum", dict(type=float, help="Natural gradient: SPRING's momentum mu, 0 <= mu < 1 (0: the memoryless step).")),
 ]
 # (flags, dest, default expression on the get_parser keywords, help)
 _SWITCHES = [
@@ -86,7 +87,7 @@ _DEFAULTS = dict(molecule="molecules/H2", hamiltonian_fname=None, out=None, numb
                  pretrained_model_loc=None, cont=False, n_excitations_max=-1, comb_amp_phase=False,
                  use_amp_spin_sym=True, use_phase_spin_sym=False, aggregate_phase=True, restrict_H=True,
                  reset_opt=False, verbose=False, seed=-1, exact_eloc=False, train_exact_eloc=False,
-                 sr=False, sr_shift=1e-3, sr_lr=0.1, sr_solver=None)
+                 sr=False, sr_shift=1e-3, sr_lr=0.1, sr_solver=None, sr_momentum=0.0)
 
 
 def get_parser(**overrides):
@@ -184,9 +185,11 @@ def _run(molecule_fname, hamiltonian_fname, exp_name, num_experiments, pretraine
          reweight_samples_by_psi, n_train, n_pretrain, output_freq, save_freq, n_lut, n_hid, n_layer, n_hid_phase,
          n_layer_phase, n_excitations_max, comb_amp_phase, use_amp_spin_sym, use_phase_spin_sym, aggregate_phase,
          use_restrictedH, loadH, presolveH, overwrite_pauli_hamiltonian, verbose, seed, device=None, exact_eloc=False,
-         train_exact_eloc=False, sr=False, sr_shift=1e-3, sr_lr=0.1, sr_solver=None):
+         train_exact_eloc=False, sr=False, sr_shift=1e-3, sr_lr=0.1, sr_solver=None, sr_momentum=0.0):
     if sr_solver is not None and not sr:
         raise ValueError("-sr_solver chooses the solver of -sr (natural gradient): give -sr as well")
+    if sr_momentum and not sr:
+        raise ValueError("-sr_momentum sets the momentum of -sr (natural gradient): give -sr as well")
     if sr and (comb_amp_phase or n_layer != 1 or n_lut):
         raise NotImplementedError("-sr (natural gradient): single-phase and aggregate-phase networks with one hidden layer per block "
                                   "only; -comb_amp_phase shares the last block's first layer between amplitude and phase, and "
@@ -210,7 +213,8 @@ def _run(molecule_fname, hamiltonian_fname, exp_name, num_experiments, pretraine
                            n_unq_samps_min, n_unq_samps_max, n_train, n_pretrain, output_freq, save_freq, n_lut, n_hid, n_layer,
                            n_hid_phase, n_layer_phase, comb_amp_phase, use_amp_spin_sym, use_phase_spin_sym, aggregate_phase,
                            use_restrictedH, presolveH, verbose, seed, device, exact_eloc, train_exact_eloc,
-                           dict(dict(diag_shift=sr_shift, lr=sr_lr), **({} if sr_solver is None else dict(solver=sr_solver))) if sr else None)
+                           dict(dict(diag_shift=sr_shift, lr=sr_lr), **({} if sr_solver is None else dict(solver=sr_solver)),
+                                **(dict(momentum=sr_momentum) if sr_momentum else {})) if sr else None)
     finally:
         if locked[0]:
             _SETUP_LOCK.release()
@@ -444,6 +448,8 @@ def run_from_parser(parser, argv=None):
         raise Exception("Invalid option combination: at most one of -no_mask_psi and -full_mask_psi can be specified.")
     if args.sr_solver is not None and not args.sr:
         raise ValueError("-sr_solver chooses the solver of -sr (natural gradient): give -sr as well")
+    if args.sr_momentum and not args.sr:
+        raise ValueError("-sr_momentum sets the momentum of -sr (natural gradient): give -sr as well")
     if args.farm and "WORLD_SIZE" not in os.environ and (args.per_gpu > 1 or args.seeds or args.farm_gpus > 0):
         return _farm_launch(args, argv)
     rank, world = _setup_distributed(args.farm, args.per_gpu)
@@ -477,7 +483,7 @@ def _run_job(args, molecule_fname, seed):
             continue
         if key in ("sr_shift", "sr_lr") and not args.sr:
             continue
-        if key == "sr_solver" and val is None:
+        if (key == "sr_solver" and val is None) or (key == "sr_momentum" and not val):
             continue
         print(f"\t{key} : {val}")
     print("")
@@ -495,7 +501,8 @@ def _run_job(args, molecule_fname, seed):
                 use_restrictedH=not args.no_restrictedH, loadH=args.loadH, presolveH=args.presolveH,
                 overwrite_pauli_hamiltonian=args.overwriteH, verbose=args.verbose, seed=seed, exact_eloc=args.exact_eloc,
                 train_exact_eloc=args.train_exact_eloc, **(dict(sr=True, sr_shift=args.sr_shift, sr_lr=args.sr_lr) if args.sr else {}),
-                **({} if args.sr_solver is None else dict(sr_solver=args.sr_solver)))
+                **({} if args.sr_solver is None else dict(sr_solver=args.sr_solver)),
+                **(dict(sr_momentum=args.sr_momentum) if args.sr_momentum else {}))
 
 
 def run(*args, **kwargs):

@@ -382,6 +382,25 @@ class FusedLogPsi:
         return out
 
     @torch.no_grad()
+    def sr_jvp(self, saved, v):
+        """(A v, B v) for the table of ``forward_saved`` (HIP mode; ``saved`` its token) and a flat vector ``v`` [n_params] in
+        state_dict order (``naqs_net_sr_jvp``): float64 [M] on the device, uncentred.  A = d log|psi| / d theta, B = d phase / d theta;
+        no Jacobian is formed (per layer the factors of ``sr_gram`` against v's slice)."""
+        self._sr_check()
+        keys = saved[0]
+        if saved[1] is not None:
+            raise NotImplementedError("sr_jvp needs the token of forward_saved in HIP mode")
+        M = keys.shape[0]
+        v = v.to(device=self.device, dtype=torch.float32).contiguous()
+        if v.shape != (self.n_params,):
+            raise ValueError(f"sr_jvp: v has shape {tuple(v.shape)}, not ({self.n_params},)")
+        ua = torch.empty(M, dtype=torch.float64, device=self.device)
+        up = torch.empty(M, dtype=torch.float64, device=self.device)
+        st = self._lib.naqs_net_sr_jvp(self._h, M, keys.data_ptr(), v.data_ptr(), ua.data_ptr(), up.data_ptr(), _stream_ptr(self.device))
+        _lib.check(st, "naqs_net_sr_jvp")
+        return ua, up
+
+    @torch.no_grad()
     def sr_solve(self, Ta, Tp, ya, yp):
         """T x = y for the systems of ``sr_gram`` by the library's blocked float64 Cholesky (``naqs_net_sr_solve``) -> (x_a, x_phi,
         info).  ``Ta`` and ``Tp`` are OVERWRITTEN: on return their lower triangles (with the diagonal) hold the factors L, the

@@ -339,6 +339,7 @@ class OptimizerBase:
         self.run_time = 0
 
     def reset_optimizer(self, cond_idx=None):
+        self._sr_phi_prev = None               # (natural gradient with momentum: the previous step)
         self._onecall_cached = None            # (a plain torch optimiser cannot take the one-call step)
         if isinstance(self.optimizer_args, dict):
             self.optimizer = self.optimizer_callable(self.wavefunction.conditional_parameters(cond_idx),
@@ -815,29 +816,48 @@ class OptimizerBase:
     def _natural_gradient_update(self, fused, saved, w, g):
         """theta -= lr * [X_a^T (T_a + lambda I)^-1 y_a + X_phi^T (T_phi + lambda I)^-1 y_phi] (``FusedLogPsi.sr_gram`` /
         ``sr_direction``); the two solves are torch's Cholesky in float64 on the device, or with ``solver="hip"`` the library's
-        (``FusedLogPsi.sr_solve``).  A factorisation that reports failure raises ``NaturalGradientError``; nothing is retried."""
+        (``FusedLogPsi.sr_solve``).  A factorisation that reports failure raises ``NaturalGradientError``; nothing is retried.
+        With ``momentum`` mu > 0 and a previous step phi_prev (SPRING): the right-hand sides become y - mu X phi_prev
+        (``FusedLogPsi.sr_jvp``) and the step phi = mu phi_prev + the solve's direction; theta -= lr * phi.  mu = 0, no
+        ``momentum`` or the first step: the plain step, call for call."""
         ng = self.natural_gradient
+        mu = float(ng.get("momentum", 0.0))
+        prev = getattr(self, "_sr_phi_prev", None) if mu > 0 else None
         Ta, Tp, ya, yp = fused.sr_gram(saved, w, g, ng["diag_shift"])
+        extra = {}
+        if prev is not None:
+            # SPRING: regularise towards mu phi_prev instead of 0 — the same two systems with the right-hand sides
+            # y - mu X phi_prev, X phi_prev = sqrt(w) o (u - w^T u) from the Jacobian-vector products u = (A phi_prev, B phi_prev)
+            ua, up = fused.sr_jvp(saved, prev)
+            wd = w.to(torch.float64)
+            sw = wd.sqrt()
+            ya = ya - mu * sw * (ua - wd @ ua)
+            yp = yp - mu * sw * (up - wd @ up)
+            extra["jvp_norm"] = torch.sqrt(ua @ ua + up @ up)
+        M = int(Ta.shape[0])
         if ng.get("solver", "torch") == "hip":
+            solver = "hip"
             xa, xp, info = fused.sr_solve(Ta, Tp, ya, yp)
             for name, minor in zip(("amplitude", "phase"), info.tolist()):
                 if minor != 0:
-                    raise NaturalGradientError(f"natural gradient: Cholesky of the {name} block ({Ta.shape[0]} x {Ta.shape[0]}, "
+                    raise NaturalGradientError(f"natural gradient: Cholesky of the {name} block ({M} x {M}, "
                                                f"diag_shift {ng['diag_shift']:g}) failed at leading minor {minor}")
-            direction = fused.sr_direction(saved, w, xa, xp)
-            self.wavefunction.flatten_parameters().add_(direction, alpha=-float(ng["lr"]))
-            self.sr_last = dict(M=int(Ta.shape[0]), direction_norm=direction.norm(), solver="hip")
-            return
-        xs = []
-        for name, T, y in (("amplitude", Ta, ya), ("phase", Tp, yp)):
-            L, info = torch.linalg.cholesky_ex(T)
-            if int(info.item()) != 0:
-                raise NaturalGradientError(f"natural gradient: Cholesky of the {name} block ({T.shape[0]} x {T.shape[0]}, "
-                                           f"diag_shift {ng['diag_shift']:g}) failed at leading minor {int(info.item())}")
-            xs.append(torch.cholesky_solve(y.unsqueeze(1), L).squeeze(1))
-        direction = fused.sr_direction(saved, w, xs[0], xs[1])
+        else:
+            solver, xs = "torch", []
+            for name, T, y in (("amplitude", Ta, ya), ("phase", Tp, yp)):
+                L, info = torch.linalg.cholesky_ex(T)
+                if int(info.item()) != 0:
+                    raise NaturalGradientError(f"natural gradient: Cholesky of the {name} block ({M} x {M}, "
+                                               f"diag_shift {ng['diag_shift']:g}) failed at leading minor {int(info.item())}")
+                xs.append(torch.cholesky_solve(y.unsqueeze(1), L).squeeze(1))
+            xa, xp = xs
+        direction = fused.sr_direction(saved, w, xa, xp)
+        if prev is not None:
+            direction.add_(prev, alpha=mu)                    # phi = mu phi_prev + the solve's direction
         self.wavefunction.flatten_parameters().add_(direction, alpha=-float(ng["lr"]))
-        self.sr_last = dict(M=int(T.shape[0]), direction_norm=direction.norm(), solver="torch")
+        if mu > 0:
+            self._sr_phi_prev = direction
+        self.sr_last = dict(M=M, direction_norm=direction.norm(), solver=solver, momentum=mu, **extra)
 
     # ---- checkpoints / logs: same keys as the reference (energy.py:400-538) ----
     def _fmt(self, fname):
@@ -857,10 +877,13 @@ class OptimizerBase:
         if d:
             os.makedirs(d, exist_ok=True)
         wf_fname = self.wavefunction.save(os.path.splitext(fname)[0] + '_naqs', quiet)
-        torch.save({'optimizer:state_dict': self.optimizer.state_dict(), 'run_time': self.run_time,
-                    'n_steps': self.n_steps, 'n_epochs': self.n_epochs, 'log': self.log,
-                    'sampled_idxs': self.sampled_idxs, 'wavefunction:fname': wf_fname,
-                    'hamiltonian_fname': self.pauli_hamiltonian_fname}, fname)
+        ck = {'optimizer:state_dict': self.optimizer.state_dict(), 'run_time': self.run_time,
+              'n_steps': self.n_steps, 'n_epochs': self.n_epochs, 'log': self.log,
+              'sampled_idxs': self.sampled_idxs, 'wavefunction:fname': wf_fname,
+              'hamiltonian_fname': self.pauli_hamiltonian_fname}
+        if (getattr(self, "natural_gradient", None) or {}).get("momentum", 0.0) > 0:
+            ck['natural_gradient:phi_prev'] = getattr(self, "_sr_phi_prev", None)      # the previous step (None before the first)
+        torch.save(ck, fname)
         if not quiet:
             print(f"Saving checkpoint {fname}...done.")
 
@@ -884,6 +907,9 @@ class OptimizerBase:
             print("\tOptimizer could not be loaded.")
         self.log, self.n_steps, self.n_epochs = ck['log'], ck['n_steps'], ck['n_epochs']
         self.run_time, self.sampled_idxs = ck['run_time'], ck['sampled_idxs']
+        if (getattr(self, "natural_gradient", None) or {}).get("momentum", 0.0) > 0:
+            prev = ck.get('natural_gradient:phi_prev')                                  # absent: the next step is a plain one
+            self._sr_phi_prev = None if prev is None else prev.to(device=self.device, dtype=torch.float32)
         if not quiet:
             print(f"Loading checkpoint {fname}...done.")
 
@@ -909,12 +935,16 @@ class PartialSamplingOptimizer(OptimizerBase):
                  log_exact_energy=True, exact_local_energies=False, natural_gradient=None, **kwargs):
         # natural_gradient: None (Adam, as always) or dict(diag_shift=..., lr=...[, solver="torch" | "hip"]): stochastic
         # reconfiguration in sample space (minSR) on the Gram kernels of naqs_sr.hip; the optimiser passed in optimizer= is then
-        # never stepped.  solver: who solves the two systems — torch's Cholesky (the default) or naqs_net_sr_solve
+        # never stepped.  solver: who solves the two systems — torch's Cholesky (the default) or naqs_net_sr_solve.  momentum: SPRING's
+        # mu (0 or absent: the memoryless step) — the previous step is kept and the solve regularised towards mu times it
         if natural_gradient is not None:
             natural_gradient = dict(natural_gradient)
-            if set(natural_gradient) - {"solver"} != {"diag_shift", "lr"} or natural_gradient.get("solver", "torch") not in ("torch", "hip") \
-                    or not natural_gradient["diag_shift"] > 0 or not natural_gradient["lr"] > 0:
-                raise ValueError('natural_gradient: dict(diag_shift > 0, lr > 0[, solver="torch" | "hip"])')
+            mu = natural_gradient.get("momentum", 0.0)
+            if set(natural_gradient) - {"solver", "momentum"} != {"diag_shift", "lr"} \
+                    or natural_gradient.get("solver", "torch") not in ("torch", "hip") \
+                    or not natural_gradient["diag_shift"] > 0 or not natural_gradient["lr"] > 0 \
+                    or isinstance(mu, bool) or not isinstance(mu, (int, float)) or not 0 <= mu < 1:
+                raise ValueError('natural_gradient: dict(diag_shift > 0, lr > 0[, solver="torch" | "hip"][, 0 <= momentum < 1])')
         self.natural_gradient = natural_gradient
         kwargs['reweight_samples_by_psi'] = False
         super().__init__(exact_local_energies=exact_local_energies, **kwargs)

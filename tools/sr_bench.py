@@ -4,11 +4,13 @@ steps / wall time to an energy with the natural gradient and with Adam from the 
     python tools/sr_bench.py [--rows 1500,10000] [--reps 20]                  the calls of one step (HIP events around each call)
     python tools/sr_bench.py --converge LiH --target -7.8810 --max-steps 500  steps and seconds until <E> of a step <= target
                              [--sr-solver hip]                                with the library's Cholesky solve
+                             [--sr-momentum 0.9]                              with SPRING's momentum
 
 The calls: the training forward; naqs_net_sr_gram_uncentred (the factor kernels + sr_gram_kernel twice); naqs_net_sr_gram (the same
 + row sums and centring); the two float64 Cholesky solves, by torch and by naqs_net_sr_solve — measured alternately in the same
 call, three rounds, each repetition on fresh copies of T because the solve overwrites it (the copies are outside the timed
-region); naqs_net_sr_direction (seeds + the training backward).
+region); naqs_net_sr_direction (seeds + the training backward); naqs_net_sr_jvp (the factor kernels + sr_jvp_kernel twice: the
+call a step with momentum adds), alternately with naqs_net_sr_gram, three rounds.
 sr_gram_kernel's share of the f64-MFMA peak is computed from the uncentred call (an upper bound of the kernel's time); run under
 `rocprofv3 --kernel-trace --stats -- python tools/sr_bench.py --rows 1500` for the per-kernel split.
 """
@@ -118,12 +120,25 @@ def step_calls(rows, reps):
     solve_flops = 2.0 * (rows ** 3 / 3.0 + 2.0 * rows ** 2)
     hip_vs_torch = [float(((h - x).abs().max() / x.abs().max()).item()) for h, x in ((ha, xa), (hp, xp))]
     t_dir, _ = _timed(lambda: fused.sr_direction(saved, w, xa, xp), reps)
+    # the momentum step's extra call (naqs_net_sr_jvp: the factor kernels + sr_jvp_kernel twice) alternately with the plain step's
+    # own Gram call, three rounds in this one process
+    v = torch.as_tensor(rs.normal(0, 1e-2, fused.n_params), dtype=torch.float32, device="cuda")
+    rounds_jvp, rounds_gram = [], []
+    for _ in range(3):
+        rounds_gram.append(_timed(lambda: fused.sr_gram(saved, w, g, 1e-3), reps)[0])
+        rounds_jvp.append(_timed(lambda: fused.sr_jvp(saved, v), reps)[0])
+    n0 = lib.naqs_launch_count()
+    fused.sr_jvp(saved, v)
+    jvp_launches = lib.naqs_launch_count() - n0
     flops = gram_flops(hil.N // 2, 64, (512, 512), rows)
     return dict(what="N2 natural-gradient step, per call", rows=rows, us_forward=t_fwd, us_factors_and_gram=t_unc,
                 us_gram_and_centring=t_gram, us_two_cholesky_solves=t_solve, us_direction=t_dir,
                 us_two_cholesky_solves_rounds=rounds_torch, us_two_hip_solves_rounds=rounds_hip,
                 us_two_hip_solves=float(np.median(rounds_hip)), hip_solve_launches=int(solve_launches),
-                us_step_hip=t_fwd + t_gram + float(np.median(rounds_hip)) + t_dir, solve_gflop=solve_flops / 1e9,
+                us_step_hip=t_fwd + t_gram + float(np.median(rounds_hip)) + t_dir,
+                us_jvp=float(np.median(rounds_jvp)), us_jvp_rounds=rounds_jvp, us_gram_and_centring_rounds=rounds_gram,
+                jvp_launches=int(jvp_launches),
+                us_step_hip_with_momentum=t_fwd + t_gram + float(np.median(rounds_jvp)) + float(np.median(rounds_hip)) + t_dir, solve_gflop=solve_flops / 1e9,
                 hip_solve_fraction_of_f64_mfma_peak=solve_flops / (float(np.median(rounds_hip)) * 1e-6) / PEAK_F64_MFMA,
                 hip_vs_torch_max_rel_diff=hip_vs_torch,
                 us_step=t_fwd + t_gram + t_solve + t_dir, gram_gflop=flops / 1e9,
@@ -170,9 +185,11 @@ def main():
     ap.add_argument("--sr-shift", type=float, default=1e-3)
     ap.add_argument("--sr-lr", type=float, default=0.1)
     ap.add_argument("--sr-solver", choices=["torch", "hip"], default=None)
+    ap.add_argument("--sr-momentum", type=float, default=0.0)
     a = ap.parse_args()
     if a.converge:
-        for ng in (dict(dict(diag_shift=a.sr_shift, lr=a.sr_lr), **({"solver": a.sr_solver} if a.sr_solver else {})), None):
+        for ng in (dict(dict(diag_shift=a.sr_shift, lr=a.sr_lr), **({"solver": a.sr_solver} if a.sr_solver else {}),
+                        **({"momentum": a.sr_momentum} if a.sr_momentum else {})), None):
             print(json.dumps(converge(a.converge, a.target, a.max_steps, ng, int(a.n_samples))), flush=True)
         return
     for rows in (int(r) for r in a.rows.split(",")):
