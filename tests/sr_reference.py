@@ -17,6 +17,9 @@ Definitions (include/naqs_hip.h, naqs_net_sr_gram): log psi_i = a_i + i phi_i, A
                                          tables of up to 4 300 rows (tests/test_sr_scale_gpu.py): G_ij depends on rows i and j
                                          alone, so the float64 Jacobian rows of ~80 sampled rows check G[R][:, R] at any M; the
                                          centring is ``centred`` of the device's own G; X^T x is one float64 backward with seeds.
+* ``SHAPE_CASES`` / ``SYM_CASES`` / ``ORDER_CASES`` / ``shape_net`` / ``shape_id`` / ``SEEDS``
+                                         every phase width and depth class, -phase_sym in both families and orderings other than
+                                         -1 (tests/test_sr_shapes.py, tests/test_sr_shapes_gpu.py), tables of at most 130 rows.
 """
 import numpy as np
 import torch
@@ -62,6 +65,88 @@ WIDTH_CASES = [("LiH", agg, ha, (32,), True, "PARTIAL") for agg in (False, True)
 WIDTH_ROWS = (65, 200)
 
 
+# ---- every phase shape the natural-gradient entries accept (tests/test_sr_shapes.py, tests/test_sr_shapes_gpu.py) ----
+# (sector, aggregate, amp_hidden, phase_hidden, PHASE_sym, masking): the amplitude symmetry is on throughout (``shape_net`` builds
+# on grad_reference.sector_net).  sr_gram_kernel reads kd = pad32(N) columns of a layer's deltas and ka = pad32(K) of its inputs
+# out of the training scratch, whose leading dimensions are pad64; sr_jvp_kernel deals (layer, 64 columns) items to at most 16
+# workgroups per tile.  Each shape is named for the branch it reaches.
+_SHAPES = [
+    ((1,), "one chunk, 31 padding columns read"),
+    ((5,), "one chunk, 27 padding columns read"),
+    ((33,), "two chunks, the second 31 padding columns"),
+    ((48,), "two chunks, 16 padding columns read of leading dimension 64"),
+    ((17, 17), "hidden to hidden with padding: kd and ka both 32 for 17"),
+    ((100, 200), "128 and 224 columns read from leading dimensions 128 and 256"),
+    ((96, 96), "a multiple of 32, not of 64: leading dimension 128, 96 columns read"),
+    ((160, 32), "leading dimension 192, 160 columns read"),
+    ((496, 496), "512 columns read, 16 of them padding; 17 JVP items: the deal wraps"),
+    ((512, 512), "the published shape; 17 JVP items"),
+    ((512, 512, 512), "25 JVP items, depth 3"),
+    ((16,) * 8, "9 jobs through phase_src_off"),
+    ((64,) * 8, "9 jobs, no padding"),
+]
+SHAPE_CASES = [("LiH", False, 16, ph, False, "PARTIAL") for ph, _ in _SHAPES] + [
+    ("H2", False, 16, (48,), False, "PARTIAL"),                  # 2 phase inputs, 4 states
+    ("H2", False, 16, (512, 512), False, "PARTIAL"),
+    ("syn32_8_8", False, 16, (48,), False, "PARTIAL"),           # 30 phase inputs, bit 31 of the keys
+    ("syn32_8_8", False, 16, (512, 512), False, "PARTIAL"),
+    ("LiH", False, 64, (512, 512), False, "PARTIAL"),            # the published network
+]
+SYM_CASES = [
+    ("LiH", False, 16, (16, 16), True, "PARTIAL"),
+    ("LiH", False, 16, (48,), True, "PARTIAL"),
+    ("LiH", False, 16, (112,), True, "PARTIAL"),
+    ("LiH", False, 16, (512, 512), True, "PARTIAL"),
+    ("syn10_3_2", False, 16, (48,), True, "PARTIAL"),            # open shell: the abits > bbits swap is not symmetric
+    ("LiH", True, 16, (32,), True, "PARTIAL"),
+    ("syn10_3_2", True, 16, (32,), True, "FULL"),
+    ("LiH", True, 64, (48,), True, "FULL"),
+    ("syn10_3_2", True, 64, (48,), True, "PARTIAL"),
+]
+# (index into CASES, ordering: +1 or "pi" = grad_reference.pair_ordering(P, ORDER_SEED)): LiH single [64, 64], LiH aggregate,
+# syn32_8_8 single — held to float64 at -1 by tests/test_sr_gpu.py, here bit for bit against that handle
+ORDER_CASES = [(i, o) for i in (5, 6, 7) for o in (1, "pi")]
+ORDER_SEED = 4
+SHAPE_ROWS = (1, 65, 130)       # one row, I = J with padded rows, I < J tiles; capped by the sector (H2: 4, syn10_3_2: 100)
+SHAPE_TABLE = max(SHAPE_ROWS)
+SHAPE_SEED = 3                  # make_net's default
+SEEDS = {}                      # shape_id -> seed where SHAPE_SEED leaves fewer than ``rows_wanted`` kink-free rows
+
+
+def shape_id(case):
+    name, agg, ha, ph, psym, mask = case
+    shape = "x".join(map(str, ph)) if len(set(ph)) > 1 or len(ph) < 3 else f"{ph[0]}_x{len(ph)}"
+    return f"{name}-{'agg' if agg else 'single'}-a{ha}-p{shape}-{'psym' if psym else 'nopsym'}-{mask}"
+
+
+def shape_net(case, device="cuda", qubit_ordering=-1):
+    """(hilbert, network) of a SHAPE_CASES / SYM_CASES entry, default-initialised from its seed."""
+    name, agg, ha, ph, psym, mask = case
+    return gr.sector_net(name, device=device, seed=SEEDS.get(shape_id(case), SHAPE_SEED), masking=mask, aggregate=agg, phase_sym=psym,
+                         amp_hidden=ha, phase_hidden=ph, qubit_ordering=qubit_ordering)
+
+
+def rows_wanted(hil):
+    """min(130, the sector less a tenth): what a case's kink-free table must hold."""
+    return min(SHAPE_TABLE, int(np.ceil(0.9 * hil.size)))
+
+
+def shape_rows(n):
+    return sorted({min(m, n) for m in SHAPE_ROWS})
+
+
+def order_of(o, P):
+    return o if o == 1 else gr.pair_ordering(P, ORDER_SEED)
+
+
+def split_jacobian(A, B):
+    """No parameter moves both log|psi| and the phase: (A + B, the columns that are B's) holds both in half the memory."""
+    pcols = (B != 0).any(0)
+    assert not np.any(pcols & (A != 0).any(0))
+    A += B
+    return A, pcols
+
+
 def sampled_rows(n=LARGE_ROWS, extra=64, seed=11):
     """R_all: FIXED_ROWS and ``extra`` seeded random rows of a table of ``n`` rows, ascending."""
     rs = np.random.RandomState(seed)
@@ -93,8 +178,9 @@ def case_id(case):
     return f"{name}-{'agg' if agg else 'single'}-a{ha}-p{'x'.join(map(str, ph))}-{'sym' if sym else 'nosym'}-{mask}"
 
 
-def make_net(case, device="cuda", seed=3):
-    """(hilbert, network) of a case, default-initialised from ``seed`` (the parameters are drawn on the CPU: the same on any device)."""
+def make_net(case, device="cuda", seed=3, qubit_ordering=-1):
+    """(hilbert, network) of a case, default-initialised from ``seed`` (the parameters are drawn on the CPU: the same on any device
+    and at any ``qubit_ordering``)."""
     from naqs_amd.hilbert import Encoding, Hilbert
     from naqs_amd.nade import NadeMasking
     from naqs_amd.wavefunction import NAQSComplex_NADE_orbitals
@@ -102,7 +188,7 @@ def make_net(case, device="cuda", seed=3):
     _, N, na, nb, _ = gr.sector(name)
     hil = Hilbert.get(N, na, nb, encoding=Encoding.SIGNED)
     torch.manual_seed(seed)
-    wf = NAQSComplex_NADE_orbitals(hil, device=device, qubit_ordering=-1, masking=NadeMasking[mask], amp_hidden_size=[ha],
+    wf = NAQSComplex_NADE_orbitals(hil, device=device, qubit_ordering=qubit_ordering, masking=NadeMasking[mask], amp_hidden_size=[ha],
                                    phase_hidden_size=list(ph), use_amp_spin_sym=sym, use_phase_spin_sym=False, aggregate_phase=agg,
                                    n_alpha_electrons=na, n_beta_electrons=nb)
     return hil, wf
