@@ -206,6 +206,16 @@ int naqs_prof_read(naqs_ham_t *h, double *total_ms, int64_t *launches);
 /* Name (with template arguments) of the local-energy kernel the handle's most recent call launched, e.g.
  * "eloc_kernel2<uint32_t, STAGE=2, NT=1024, BLOOM=0>"; empty before the first call.  Measurement aid (bench.py). */
 int naqs_ham_last_kernel(const naqs_ham_t *h, char *buf, int buf_len);
+/* How the handle's non-diagonal groups are evaluated by the default local-energy kernel: out[0] class D (double
+ * excitations, one 16-entry sign table each), out[1] class S (single excitations, per-segment tables), out[2] class L
+ * (the term loop), out[3] the bytes of the tables.  NAQS_ELOC_CLOSED=0 at creation puts every group in class L. */
+int naqs_ham_closed_counts(const naqs_ham_t *h, int64_t out[4]);
+/* The class and the table of ONE group (the terms that share the flip mask xy, in the order the handle keeps them: ascending
+ * input position), as naqs_ham_create builds them; no device needed.  class_out: 0 L, 1 D, 2 S; ref_out: the reference
+ * mask R; table_out (may be NULL): 16 doubles for class D, 4 * 64 * ceil(n_qubits / 6) for class S laid out
+ * [segment][pattern][key slice], untouched for class L. */
+int naqs_closed_group(int n_qubits, uint64_t xy, int64_t n_terms, const uint64_t *yz, const double *coeff,
+                      int32_t *class_out, uint64_t *ref_out, double *table_out);
 /* Record only every stride-th launch (default 1): an event pair costs a few microseconds of queue time,
  * so a sparse sample keeps the timed region representative. */
 int naqs_prof_stride(naqs_ham_t *h, int stride);

@@ -42,6 +42,9 @@ SIGNATURES = {
     "naqs_hij_from_parity": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, ctypes.c_int, c_vp, c_vp]),
     "naqs_csr_mv": (ctypes.c_int, [c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "naqs_ham_last_kernel": (ctypes.c_int, [c_vp, ctypes.c_char_p, ctypes.c_int]),
+    "naqs_closed_group": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint64, c_i64, c_vp, c_vp, ctypes.POINTER(ctypes.c_int32),
+                                         ctypes.POINTER(ctypes.c_uint64), c_vp]),
+    "naqs_ham_closed_counts": (ctypes.c_int, [c_vp, ctypes.POINTER(c_i64 * 4)]),
     "naqs_net_last_kernel": (ctypes.c_int, [c_vp, ctypes.c_char_p, ctypes.c_int]),
     "naqs_prof_enable": (ctypes.c_int, [c_vp, ctypes.c_int]),
     "naqs_prof_read": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_i64)]),

@@ -286,6 +286,12 @@ class DevicePauliHamiltonian:
         _lib.check(self._lib.naqs_ham_last_kernel(self._h, buf, 128), "naqs_ham_last_kernel")
         return buf.value.decode()
 
+    def closed_counts(self):
+        """(class D groups, class S groups, class L groups, table bytes) of the default kernel's view of this handle."""
+        out = (ctypes.c_int64 * 4)()
+        _lib.check(self._lib.naqs_ham_closed_counts(self._h, ctypes.byref(out)), "naqs_ham_closed_counts")
+        return tuple(int(v) for v in out)
+
 
 def popcount_parity_device(arr):
     """Device counterpart of src.utils.hamiltonian_math.popcount_parity: int8 tensor, same shape.
