@@ -169,6 +169,31 @@ int naqs_hmatvec(naqs_ham_t *h, int64_t M, const uint64_t *keys_dev, const doubl
 int naqs_ham_connected(naqs_ham_t *h, int64_t M, const uint64_t *keys_dev, int64_t row_begin, int64_t n_rows,
                        int64_t capacity, uint64_t *out_keys_dev, int64_t *count_dev, void *stream);
 
+/*
+ * Second-order Epstein-Nesbet terms of rows that need not be table rows.  The table S is keys_dev[M] (unique, physical, any
+ * order, as for naqs_eloc) with real coefficients c_dev[M]; ext_keys_dev[n_ext] are the row keys (physical; usually the set
+ * naqs_ham_connected returns, but a key of the table is allowed).  Per row a, both arrays optional (null: not returned):
+ *   num_dev[a]  = sum over the non-diagonal XY groups g of H[a, a ^ xy_g] c[a ^ xy_g], over the partners the table holds —
+ *                 the row walk of the E_loc kernel without its diagonal term and without a division; H[a, j] has the bits
+ *                 naqs_eloc gives it;
+ *   diag_dev[a] = H[a, a], the xy == 0 group (0 when the handle has none).
+ * out4_dev[4] (mandatory), with den_a = e0 - diag_a:
+ *   [0] sum over den_a < 0 of num_a^2 / den_a  (E_PT2 when e0 is the subspace energy and the rows its external set),
+ *   [1] sum over den_a < 0 of num_a^2,
+ *   [2] the number of rows with den_a >= 0 or NaN ("intruders"), as a double,
+ *   [3] sum of num_a^2 over those rows.
+ * Intruder rows never enter [0]: nothing is divided by a non-negative denominator.  The sums are taken in one fixed order (no
+ * floating-point atomics): the same bits on repetition.  A row's num and diag depend on its key, the SET of table keys and c
+ * only — not on the table's order, the other rows or the kernel form (NAQS_STAGE, NAQS_BLOCK, the Bloom filter).
+ * n_ext = 0: out4 = 0, NAQS_OK.  M < 1, n_ext < 0, a null required pointer or a non-finite e0: NAQS_ERR_INVALID.
+ * M > 2^24 - 1 (as naqs_eloc) or n_ext > 2^30: NAQS_ERR_UNSUPPORTED.
+ * The call rebuilds the handle's sample-key table (like naqs_eloc).  It stands in for no reference code: the reference stops
+ * at the variational subspace energy of solve_H (src/optimizer/energy.py:762-786).
+ */
+int naqs_ham_pt2(naqs_ham_t *h, int64_t M, const uint64_t *keys_dev, const double *c_dev, double e0,
+                 int64_t n_ext, const uint64_t *ext_keys_dev,
+                 double *num_dev, double *diag_dev, double *out4_dev, void *stream);
+
 /* ---- inner ring: device versions of the three Cython entry points the reference imports ---- */
 
 /* src.utils.hamiltonian_math.popcount_parity (hamiltonian_math.pyx:455-484):

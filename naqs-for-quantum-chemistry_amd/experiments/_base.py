@@ -78,6 +78,8 @@ _SWITCHES = [
     (("-train_exact_eloc",), "train_exact_eloc", lambda k: k["train_exact_eloc"],
      "Train on exact local energies (psi on every connected state)"),
     (("-sr",), "sr", lambda k: k["sr"], "Train with the natural gradient (stochastic reconfiguration in sample space, minSR)."),
+    (("-pt2",), "pt2", lambda k: k["pt2"],
+     "After training, add the second-order Epstein-Nesbet correction over the connected states to the sampled-subspace energy."),
 ]
 _DEFAULTS = dict(molecule="molecules/H2", hamiltonian_fname=None, out=None, number=1, qubit_ordering=-1, lr=-1,
                  lr_lut=1e-2, n_samps=1e6, n_samps_max=1e12, n_unq_samps_min=50000, n_unq_samps_max=1e5,
@@ -87,7 +89,7 @@ _DEFAULTS = dict(molecule="molecules/H2", hamiltonian_fname=None, out=None, numb
                  pretrained_model_loc=None, cont=False, n_excitations_max=-1, comb_amp_phase=False,
                  use_amp_spin_sym=True, use_phase_spin_sym=False, aggregate_phase=True, restrict_H=True,
                  reset_opt=False, verbose=False, seed=-1, exact_eloc=False, train_exact_eloc=False,
-                 sr=False, sr_shift=1e-3, sr_lr=0.1, sr_solver=None, sr_momentum=0.0)
+                 sr=False, sr_shift=1e-3, sr_lr=0.1, sr_solver=None, sr_momentum=0.0, pt2=False)
 
 
 def get_parser(**overrides):
@@ -185,7 +187,7 @@ def _run(molecule_fname, hamiltonian_fname, exp_name, num_experiments, pretraine
          reweight_samples_by_psi, n_train, n_pretrain, output_freq, save_freq, n_lut, n_hid, n_layer, n_hid_phase,
          n_layer_phase, n_excitations_max, comb_amp_phase, use_amp_spin_sym, use_phase_spin_sym, aggregate_phase,
          use_restrictedH, loadH, presolveH, overwrite_pauli_hamiltonian, verbose, seed, device=None, exact_eloc=False,
-         train_exact_eloc=False, sr=False, sr_shift=1e-3, sr_lr=0.1, sr_solver=None, sr_momentum=0.0):
+         train_exact_eloc=False, sr=False, sr_shift=1e-3, sr_lr=0.1, sr_solver=None, sr_momentum=0.0, pt2=False):
     if sr_solver is not None and not sr:
         raise ValueError("-sr_solver chooses the solver of -sr (natural gradient): give -sr as well")
     if sr_momentum and not sr:
@@ -214,7 +216,7 @@ def _run(molecule_fname, hamiltonian_fname, exp_name, num_experiments, pretraine
                            n_hid_phase, n_layer_phase, comb_amp_phase, use_amp_spin_sym, use_phase_spin_sym, aggregate_phase,
                            use_restrictedH, presolveH, verbose, seed, device, exact_eloc, train_exact_eloc,
                            dict(dict(diag_shift=sr_shift, lr=sr_lr), **({} if sr_solver is None else dict(solver=sr_solver)),
-                                **(dict(momentum=sr_momentum) if sr_momentum else {})) if sr else None)
+                                **(dict(momentum=sr_momentum) if sr_momentum else {})) if sr else None, **(dict(pt2=True) if pt2 else {}))
     finally:
         if locked[0]:
             _SETUP_LOCK.release()
@@ -227,7 +229,7 @@ def _run_locked(locked, molecule_fname, hamiltonian_fname, exp_name, num_experim
                 reset_optimizer, qubit_ordering, masking, lr, lr_lut, n_samps, n_samps_max, n_unq_samps_min, n_unq_samps_max,
                 n_train, n_pretrain, output_freq, save_freq, n_lut, n_hid, n_layer, n_hid_phase, n_layer_phase, comb_amp_phase,
                 use_amp_spin_sym, use_phase_spin_sym, aggregate_phase, use_restrictedH, presolveH, verbose, seed, device,
-                exact_eloc=False, train_exact_eloc=False, natural_gradient=None):
+                exact_eloc=False, train_exact_eloc=False, natural_gradient=None, pt2=False):
     seed = set_global_seed(_agree_on_seed(seed))
     molecule, qubit_hamiltonian = load_molecule(molecule_fname, hamiltonian_fname=hamiltonian_fname, verbose=True)
     N = molecule.n_qubits
@@ -315,14 +317,16 @@ def _run_locked(locked, molecule_fname, hamiltonian_fname, exp_name, num_experim
                 g['lr'] = 5e-4
             opt.run(n_epochs=n_train // 2, save_freq=save_freq, save_final=True, output_freq=output_freq)
         train_time = time.time() - t0
-        eig_val, _, n_unq = opt.solve_H(n_samps=opt.n_samples, ret_n_samps=True)
+        # -pt2: the same draw serves the subspace energy and its second-order correction
+        sub = opt.solve_H_pt2(n_samps=opt.n_samples) if pt2 else None
+        eig_val, _, n_unq = (sub["eig"], sub["vec0"], sub["n_unq"]) if pt2 else opt.solve_H(n_samps=opt.n_samples, ret_n_samps=True)
         # -exact_eloc: the trained state's energy from a fresh draw with psi evaluated on every connected state
         exact = opt.evaluate_energy(n_samps=opt.n_samples, exact=True) if exact_eloc else None
-        results.append(_summarise(opt, molecule, exp_name_i, eig_val, n_unq, train_time, exact=exact))
+        results.append(_summarise(opt, molecule, exp_name_i, eig_val, n_unq, train_time, exact=exact, **(dict(pt2=sub) if pt2 else {})))
     return results
 
 
-def _summarise(opt, molecule, exp_name, eig_val, n_unq, train_time, exact=None):
+def _summarise(opt, molecule, exp_name, eig_val, n_unq, train_time, exact=None, pt2=None):
     """summary.txt next to the checkpoints (the reference's _base.py:330-390, same quantities)."""
     e = np.array([x[1] for x in opt.log[LogKey.E_LOC]])
     window = min(50, len(e))
@@ -336,10 +340,20 @@ def _summarise(opt, molecule, exp_name, eig_val, n_unq, train_time, exact=None):
              f"min <E_loc> : {float(e.min()) if len(e) else float('nan'):.8f}",
              f"sampled-subspace diagonalisation ({n_unq} states) : {eig_val:.8f}",
              f"HF : {molecule.hf_energy}", f"CCSD : {molecule.ccsd_energy}", f"FCI : {fci}"]
+    if pt2 is not None:
+        e2 = eig_val + pt2["e_pt2"]
+        extra = [f"sampled-subspace diagonalisation + Epstein-Nesbet PT2 ({pt2['n_external']} connected states) : {e2:.8f}" +
+                 (f" (error to FCI {(e2 - fci) * 1e3:.4f} mHa)" if fci is not None else "")]
+        if pt2["n_intruders"] > 0:
+            extra.append(f"PT2 : {pt2['n_intruders']} states at or above the subspace energy left out")
+        at = next(i for i, ln in enumerate(lines) if ln.startswith("sampled-subspace diagonalisation")) + 1
+        lines[at:at] = extra
     if fci is not None:
         lines.append(f"error to FCI (mHa) : {(final - fci) * 1e3:.4f}")
         lines.append(f"subspace-diag error to FCI (mHa) : {(eig_val - fci) * 1e3:.4f}")
     res = dict(final=final, fci=fci, eig=eig_val, n_unq=n_unq, time=train_time)
+    if pt2 is not None:
+        res.update(e_pt2=pt2["e_pt2"])
     if exact is not None:
         lines.append(f"VMC energy with exact local energies: {exact['E']:.8f} ± {exact['stderr']:.2e} Ha "
                      f"({exact['n_unq']} sampled + {exact['n_connected']} connected states)")
@@ -479,7 +493,7 @@ def _run_job(args, molecule_fname, seed):
     masking = NadeMasking.NONE if args.no_mask_psi else (NadeMasking.FULL if args.full_mask_psi else NadeMasking.PARTIAL)
     print(f"Running experimental script: {__file__}\nResults will be saved to: {exp_name}/\n\nscript options:")
     for key, val in sorted(vars(args).items()):
-        if key in ("exact_eloc", "train_exact_eloc", "sr") and not val:      # an opt-in of this port: without it the listing is the reference's
+        if key in ("exact_eloc", "train_exact_eloc", "sr", "pt2") and not val:      # an opt-in of this port: without it the listing is the reference's
             continue
         if key in ("sr_shift", "sr_lr") and not args.sr:
             continue
@@ -502,7 +516,7 @@ def _run_job(args, molecule_fname, seed):
                 overwrite_pauli_hamiltonian=args.overwriteH, verbose=args.verbose, seed=seed, exact_eloc=args.exact_eloc,
                 train_exact_eloc=args.train_exact_eloc, **(dict(sr=True, sr_shift=args.sr_shift, sr_lr=args.sr_lr) if args.sr else {}),
                 **({} if args.sr_solver is None else dict(sr_solver=args.sr_solver)),
-                **(dict(sr_momentum=args.sr_momentum) if args.sr_momentum else {}))
+                **(dict(sr_momentum=args.sr_momentum) if args.sr_momentum else {}), **(dict(pt2=True) if args.pt2 else {}))
 
 
 def run(*args, **kwargs):

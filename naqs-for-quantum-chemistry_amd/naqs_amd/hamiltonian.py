@@ -260,6 +260,51 @@ class DevicePauliHamiltonian:
         vec = vec / vec.norm()
         return float(theta), vec
 
+    # ---- Epstein-Nesbet second-order correction of a subspace energy -----------------------------
+    def pt2(self, keys, c, e0, ext_keys, rows=False):
+        """``naqs_ham_pt2``: for every row key a of ``ext_keys`` num_a = sum_j H_aj c_j over the table ``keys`` (off-diagonal
+        groups only) and diag_a = H_aa, and the four sums with den_a = e0 - diag_a:
+        (sum_{den<0} num^2 / den, sum_{den<0} num^2, rows with den >= 0, sum of num^2 over those rows).
+
+        keys, ext_keys : int64 device tensors; c : real float64 device tensor [M]
+        -> float64 device tensor [4]; with ``rows=True`` (out4, num [n_ext], diag [n_ext])."""
+        M, n_ext = keys.shape[0], ext_keys.shape[0]
+        if not (keys.is_cuda and ext_keys.is_cuda and keys.dtype == torch.int64 and ext_keys.dtype == torch.int64):
+            raise ValueError("keys and ext_keys must be int64 device tensors")
+        c = c.to(device=self.device, dtype=torch.float64).contiguous()
+        if c.shape != (M,):
+            raise ValueError(f"c must have shape [{M}], got {tuple(c.shape)}")
+        keys, ext_keys = keys.contiguous(), ext_keys.contiguous()
+        out4 = torch.empty(4, dtype=torch.float64, device=self.device)
+        num = torch.empty(n_ext, dtype=torch.float64, device=self.device) if rows else None
+        diag = torch.empty(n_ext, dtype=torch.float64, device=self.device) if rows else None
+        st = self._lib.naqs_ham_pt2(self._h, M, keys.data_ptr(), c.data_ptr(), float(e0), n_ext,
+                                    ext_keys.data_ptr() if n_ext else None, num.data_ptr() if rows and n_ext else None,
+                                    diag.data_ptr() if rows and n_ext else None, out4.data_ptr(), _stream_ptr(self.device))
+        _lib.check(st, "naqs_ham_pt2")
+        return (out4, num, diag) if rows else out4
+
+    @torch.no_grad()
+    def pt2_correction(self, keys, vec, e0=None, max_external=1 << 27):
+        """Second-order Epstein-Nesbet correction of the energy of ``vec`` in the subspace ``keys``:
+        E_PT2 = sum_a (sum_j H_aj vec_j)^2 / (e0 - H_aa) over the states a outside ``keys`` that one Hamiltonian term connects
+        to it (``connected_keys``).  ``e0=None``: the Rayleigh quotient of ``vec``.  An external state with H_aa >= e0 (an
+        intruder) is left out of the sum and counted.  The external set is held whole, 8 bytes a key: a set whose capacity
+        exceeds ``max_external`` keys raises ValueError.
+
+        -> dict(e0, e_pt2, n_external, n_intruders, residual2, intruder_residual2)"""
+        M = keys.shape[0]
+        vec = vec.to(device=self.device, dtype=torch.float64).contiguous()
+        if e0 is None:
+            e0 = float(torch.dot(vec, self.matvec(keys, vec)) / torch.dot(vec, vec))
+        capacity = self.connected_capacity(M, M)
+        if capacity > max_external:
+            raise ValueError(f"the connected set of {M} keys may hold {capacity} keys, more than max_external = {max_external}")
+        ext, n_ext = self.connected_keys(keys, capacity=capacity)
+        out4 = self.pt2(keys, vec, e0, ext).tolist()
+        return dict(e0=float(e0), e_pt2=out4[0], n_external=int(n_ext), n_intruders=int(out4[2]), residual2=out4[1],
+                    intruder_residual2=out4[3])
+
     # ---- inner ring ----------------------------------------------------------------------------
     def dense_hij(self, keys):
         """Device counterpart of get_Hij_cy: float64 [M, Kxy], H[i, key_i ^ xy_g]."""

@@ -1208,9 +1208,9 @@ class PartialSamplingOptimizer(OptimizerBase):
             return self.get_samples(action, lazy=lazy)
         return states, counts, probs
 
-    def solve_H(self, n_samps=None, ret_n_samps=True):
-        """Lowest eigenpair of H restricted to the sampled states (energy.py:762-786)."""
-        import scipy.sparse.linalg as spla
+    def _solve_H_keys(self, n_samps):
+        """The sample of solve_H: one draw from the optimiser's generator, cut to the solve_H_max_states most frequent
+        states.  -> (keys, unique states drawn)"""
         if n_samps is None:
             n_samps = self.get_n_samples()
         with torch.no_grad():
@@ -1220,11 +1220,21 @@ class PartialSamplingOptimizer(OptimizerBase):
         if n_unq > limit:
             print(f"Limiting number of sampled states from {n_unq} is to most likely {limit}.")
             states = states[torch.argsort(counts)[-limit:]]
-        keys = self.hilbert.state2idx(states).squeeze(-1)
+        return self.hilbert.state2idx(states).squeeze(-1), n_unq
+
+    def _solve_H_device(self, keys):
+        """Matrix-free Lanczos on the device: no sub-matrix is formed, so the reference's 10 000-state cap (there for the
+        cost of the CSR slice) is only kept as the default of solve_H_max_states.  -> (eigenvalue, device vector, device keys)"""
+        keys_dev = keys_to_device(keys, self.device)
+        val, vec = self.pauli_hamiltonian.lowest_eigenpair(keys_dev)
+        return float(val), vec, keys_dev
+
+    def solve_H(self, n_samps=None, ret_n_samps=True):
+        """Lowest eigenpair of H restricted to the sampled states (energy.py:762-786)."""
+        import scipy.sparse.linalg as spla
+        keys, n_unq = self._solve_H_keys(n_samps)
         if self.device.type == "cuda" and len(keys) >= 3:
-            # matrix-free Lanczos on the device: no sub-matrix is formed, so the reference's 10 000-state cap
-            # (there for the cost of the CSR slice) is only kept as the default of solve_H_max_states
-            val, vec = self.pauli_hamiltonian.lowest_eigenpair(keys_to_device(keys, self.device))
+            val, vec, _ = self._solve_H_device(keys)
             vec = vec.cpu().numpy()
             vec = vec * np.sign(vec[0])
             return (float(val), vec[0], n_unq) if ret_n_samps else (float(val), vec[0])
@@ -1237,6 +1247,18 @@ class PartialSamplingOptimizer(OptimizerBase):
             val, vec = w[0], v[:, 0]
         vec = vec * np.sign(vec[0])
         return (float(val), vec[0], n_unq) if ret_n_samps else (float(val), vec[0])
+
+    def solve_H_pt2(self, n_samps=None):
+        """solve_H and, on the same sample and eigenvector, the second-order Epstein-Nesbet correction over the states the
+        sample connects to (DevicePauliHamiltonian.pt2_correction): eig is variational, eig + e_pt2 is not.
+        -> dict(eig, vec0, n_unq, e_pt2, n_external, n_intruders).  Device only."""
+        if self.device.type != "cuda":
+            raise NotImplementedError("solve_H_pt2 runs on the HIP kernels (naqs_ham_pt2): there is no CPU form")
+        keys, n_unq = self._solve_H_keys(n_samps)
+        val, vec, keys_dev = self._solve_H_device(keys)
+        pt2 = self.pauli_hamiltonian.pt2_correction(keys_dev, vec, e0=val)
+        return dict(eig=val, vec0=abs(float(vec[0])), n_unq=n_unq, e_pt2=pt2["e_pt2"], n_external=pt2["n_external"],
+                    n_intruders=pt2["n_intruders"])
 
     def run(self, n_epochs, save_freq=None, save_final=False, reset_log=False, reset_optimizer=False,
             output_freq=50):
