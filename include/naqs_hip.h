@@ -194,6 +194,33 @@ int naqs_ham_pt2(naqs_ham_t *h, int64_t M, const uint64_t *keys_dev, const doubl
                  int64_t n_ext, const uint64_t *ext_keys_dev,
                  double *num_dev, double *diag_dev, double *out4_dev, void *stream);
 
+/*
+ * Selected CI: which rows of a naqs_ham_pt2 call join the subspace.  Rows a = 0 .. n_ext-1 with distinct keys ext_keys_dev[a],
+ * num_dev[a] and diag_dev[a] (what naqs_ham_pt2 writes); the rule, every operation one float64 rounding:
+ *   den_a = diag_a - e0;
+ *   a is an INTRUDER if !(den_a > 0) or num_a is NaN, and then eps_a = +inf; otherwise eps_a = (num_a * num_a) / den_a;
+ *   a is ELIGIBLE if eps_a > 0 and eps_a >= eps_min  (a row with num = +-0 never is);
+ *   k <= 0 or no eligible row: nothing is selected;  k >= the number of eligible rows: every eligible row is selected;
+ *   otherwise tau = the k-th largest eligible eps, cut = tau * (1 - tie_rtol) (the factor formed on the host, one device
+ *   multiplication), and every eligible row with eps >= cut is selected.
+ * A near-degenerate group at the cut is never split, so the count may exceed k by the size of that group; tie_rtol = 0 keeps
+ * bit-equal ties together.  The result is a function of the SET of (key, num, diag): out_keys_dev holds the selected keys in
+ * ascending row order (ascending keys when the rows are naqs_ham_connected's, sorted), count_dev[0] their number, count_dev[1]
+ * the number of intruders among them.  count_dev[0] > capacity: overflow, as naqs_ham_connected reports it — the counts are
+ * written, out_keys_dev is unspecified.  n_ext = 0: counts 0, NAQS_OK.  eps_min or tie_rtol negative or NaN, a non-finite e0,
+ * a null required pointer, n_ext < 0 or capacity < 0: NAQS_ERR_INVALID.  n_ext > 2^30: NAQS_ERR_UNSUPPORTED.
+ * tau comes from an exact radix select on the bit patterns of eps (integer atomics only): the same bits on repetition and in
+ * both kernel forms (NAQS_SELECT_FORM: 0 chosen by n_ext, 1 one workgroup and one launch, 2 tiles over many workgroups; read
+ * at every call, reported by naqs_ham_last_kernel).  Nothing is read back.  Scratch belongs to the handle; when the tiled form
+ * meets more rows than any call before it on the handle the scratch is released and allocated anew behind a device
+ * synchronisation (as naqs_ham_pt2 grows its rows) — no other call synchronises.
+ * tie_rtol is meant in [0, 1).  Beyond, the rule is applied as written and means little: at 1 the cut is 0 — every eligible row —
+ * or, with tau = +inf, NaN — no row; above 1 the cut is negative — every eligible row.
+ */
+int naqs_ham_pt2_select(naqs_ham_t *h, int64_t n_ext, const uint64_t *ext_keys_dev, const double *num_dev,
+                        const double *diag_dev, double e0, int64_t k, double eps_min, double tie_rtol,
+                        int64_t capacity, uint64_t *out_keys_dev, int64_t *count_dev /* [2] */, void *stream);
+
 /* ---- inner ring: device versions of the three Cython entry points the reference imports ---- */
 
 /* src.utils.hamiltonian_math.popcount_parity (hamiltonian_math.pyx:455-484):

@@ -91,6 +91,14 @@ int eloc_begin(naqs_ham *h, int64_t M, hipStream_t s, ElocFeed *feed);
 int eloc_main(naqs_ham *h, int64_t M, const ElocFeed &feed, double *eloc_dev, const double *w_dev, double *out4_dev,
               hipStream_t s);
 int ham_device(const naqs_ham *h);
+// naqs_ham_pt2_select (naqs_select.hip): the handle owns its scratch (histograms and per-tile words of the multi-workgroup form,
+// grown there on demand, freed by naqs_ham_destroy) and reports its form through naqs_ham_last_kernel
+struct SelectScratch {
+    uint32_t *words = nullptr;
+    int64_t tiles = 0;
+};
+SelectScratch *ham_select_scratch(naqs_ham *h);
+void ham_set_last_kernel(naqs_ham *h, const char *name);
 int net_device(const naqs_net *n);           // implemented in naqs_logpsi.hip
 
 }  // namespace naqs

@@ -56,6 +56,10 @@ _VALUE_FLAGS = [
     (("-sr_solver",), "sr_solver", dict(type=str, choices=["torch", "hip"],
                                         help="Natural gradient: the two Cholesky solves by torch (the default) or by naqs_net_sr_solve.")),
     (("-sr_momentum",), "sr_momentum", dict(type=float, help="Natural gradient: SPRING's momentum mu, 0 <= mu < 1 (0: the memoryless step).")),
+    (("-sci",), "sci", dict(type=int, help="After training, N iterations of selected CI from the sampled subspace: each growth step "
+                                          "moves the connected states of largest second-order importance into it (0: off).")),
+    (("-sci_grow",), "sci_grow", dict(type=float, help="Selected CI: states added per growth step, as a fraction of the subspace (1.0).")),
+    (("-sci_start",), "sci_start", dict(type=int, help="Selected CI: start from the n most frequent sampled states (all of them).")),
 ]
 # (flags, dest, default expression on the get_parser keywords, help)
 _SWITCHES = [
@@ -89,7 +93,7 @@ _DEFAULTS = dict(molecule="molecules/H2", hamiltonian_fname=None, out=None, numb
                  pretrained_model_loc=None, cont=False, n_excitations_max=-1, comb_amp_phase=False,
                  use_amp_spin_sym=True, use_phase_spin_sym=False, aggregate_phase=True, restrict_H=True,
                  reset_opt=False, verbose=False, seed=-1, exact_eloc=False, train_exact_eloc=False,
-                 sr=False, sr_shift=1e-3, sr_lr=0.1, sr_solver=None, sr_momentum=0.0, pt2=False)
+                 sr=False, sr_shift=1e-3, sr_lr=0.1, sr_solver=None, sr_momentum=0.0, pt2=False, sci=0, sci_grow=None, sci_start=None)
 
 
 def get_parser(**overrides):
@@ -187,7 +191,9 @@ def _run(molecule_fname, hamiltonian_fname, exp_name, num_experiments, pretraine
          reweight_samples_by_psi, n_train, n_pretrain, output_freq, save_freq, n_lut, n_hid, n_layer, n_hid_phase,
          n_layer_phase, n_excitations_max, comb_amp_phase, use_amp_spin_sym, use_phase_spin_sym, aggregate_phase,
          use_restrictedH, loadH, presolveH, overwrite_pauli_hamiltonian, verbose, seed, device=None, exact_eloc=False,
-         train_exact_eloc=False, sr=False, sr_shift=1e-3, sr_lr=0.1, sr_solver=None, sr_momentum=0.0, pt2=False):
+         train_exact_eloc=False, sr=False, sr_shift=1e-3, sr_lr=0.1, sr_solver=None, sr_momentum=0.0, pt2=False,
+         sci=0, sci_grow=None, sci_start=None):
+    _check_sci(sci, sci_grow, sci_start)
     if sr_solver is not None and not sr:
         raise ValueError("-sr_solver chooses the solver of -sr (natural gradient): give -sr as well")
     if sr_momentum and not sr:
@@ -216,7 +222,8 @@ def _run(molecule_fname, hamiltonian_fname, exp_name, num_experiments, pretraine
                            n_hid_phase, n_layer_phase, comb_amp_phase, use_amp_spin_sym, use_phase_spin_sym, aggregate_phase,
                            use_restrictedH, presolveH, verbose, seed, device, exact_eloc, train_exact_eloc,
                            dict(dict(diag_shift=sr_shift, lr=sr_lr), **({} if sr_solver is None else dict(solver=sr_solver)),
-                                **(dict(momentum=sr_momentum) if sr_momentum else {})) if sr else None, **(dict(pt2=True) if pt2 else {}))
+                                **(dict(momentum=sr_momentum) if sr_momentum else {})) if sr else None, **(dict(pt2=True) if pt2 else {}),
+                           **(dict(sci=dict(n_iter=int(sci), grow=1.0 if sci_grow is None else float(sci_grow), n_start=sci_start)) if sci else {}))
     finally:
         if locked[0]:
             _SETUP_LOCK.release()
@@ -229,7 +236,7 @@ def _run_locked(locked, molecule_fname, hamiltonian_fname, exp_name, num_experim
                 reset_optimizer, qubit_ordering, masking, lr, lr_lut, n_samps, n_samps_max, n_unq_samps_min, n_unq_samps_max,
                 n_train, n_pretrain, output_freq, save_freq, n_lut, n_hid, n_layer, n_hid_phase, n_layer_phase, comb_amp_phase,
                 use_amp_spin_sym, use_phase_spin_sym, aggregate_phase, use_restrictedH, presolveH, verbose, seed, device,
-                exact_eloc=False, train_exact_eloc=False, natural_gradient=None, pt2=False):
+                exact_eloc=False, train_exact_eloc=False, natural_gradient=None, pt2=False, sci=None):
     seed = set_global_seed(_agree_on_seed(seed))
     molecule, qubit_hamiltonian = load_molecule(molecule_fname, hamiltonian_fname=hamiltonian_fname, verbose=True)
     N = molecule.n_qubits
@@ -318,15 +325,50 @@ def _run_locked(locked, molecule_fname, hamiltonian_fname, exp_name, num_experim
             opt.run(n_epochs=n_train // 2, save_freq=save_freq, save_final=True, output_freq=output_freq)
         train_time = time.time() - t0
         # -pt2: the same draw serves the subspace energy and its second-order correction
-        sub = opt.solve_H_pt2(n_samps=opt.n_samples) if pt2 else None
-        eig_val, _, n_unq = (sub["eig"], sub["vec0"], sub["n_unq"]) if pt2 else opt.solve_H(n_samps=opt.n_samples, ret_n_samps=True)
+        # -sci: the same draw again; its iteration 0 is solve_H_pt2's result and feeds the lines below unchanged
+        grown = opt.solve_H_sci(n_samps=opt.n_samples, **sci) if sci else None
+        if grown is not None:
+            h0 = grown["history"][0]
+            sub = dict(eig=h0["e0"], vec0=None, n_unq=grown["n_unq"], e_pt2=h0["e_pt2"], n_external=h0["n_external"],
+                       n_intruders=h0["n_intruders"])
+        else:
+            sub = opt.solve_H_pt2(n_samps=opt.n_samples) if pt2 else None
+        eig_val, _, n_unq = (sub["eig"], sub["vec0"], sub["n_unq"]) if sub is not None else opt.solve_H(n_samps=opt.n_samples, ret_n_samps=True)
         # -exact_eloc: the trained state's energy from a fresh draw with psi evaluated on every connected state
         exact = opt.evaluate_energy(n_samps=opt.n_samples, exact=True) if exact_eloc else None
-        results.append(_summarise(opt, molecule, exp_name_i, eig_val, n_unq, train_time, exact=exact, **(dict(pt2=sub) if pt2 else {})))
+        results.append(_summarise(opt, molecule, exp_name_i, eig_val, n_unq, train_time, exact=exact, **(dict(pt2=sub) if pt2 else {}),
+                                  **(dict(sci=grown) if grown is not None else {})))
     return results
 
 
-def _summarise(opt, molecule, exp_name, eig_val, n_unq, train_time, exact=None, pt2=None):
+def _check_sci(sci, sci_grow, sci_start):
+    if sci is not None and sci < 0:
+        raise ValueError("-sci takes the number of selected-CI iterations (>= 1; 0: off)")
+    if sci_grow is not None and not sci:
+        raise ValueError("-sci_grow sets the growth of -sci (selected CI): give -sci as well")
+    if sci_start is not None and not sci:
+        raise ValueError("-sci_start sets the start of -sci (selected CI): give -sci as well")
+    if sci_grow is not None and not sci_grow > 0:
+        raise ValueError("-sci_grow must be positive")
+    if sci_start is not None and sci_start < 1:
+        raise ValueError("-sci_start must be at least 1")
+
+
+def _sci_lines(sci, fci):
+    """summary.txt's lines of a selected-CI run: one per iteration, the extrapolation, the stop reason."""
+    lines = []
+    for t, h in enumerate(sci["history"]):
+        e2 = h["e0"] + h["e_pt2"]
+        lines.append(f"selected CI iteration {t} ({h['M']} states, {h['n_external']} connected) : E_S {h['e0']:.8f} , E_S + E_PT2 {e2:.8f}" +
+                     (f" (errors to FCI {(h['e0'] - fci) * 1e3:.4f} , {(e2 - fci) * 1e3:.4f} mHa)" if fci is not None else ""))
+    if sci["extrapolated"] is not None:
+        lines.append(f"selected CI extrapolated to E_PT2 = 0 (non-variational) : {sci['extrapolated']:.8f}" +
+                     (f" (error to FCI {(sci['extrapolated'] - fci) * 1e3:.4f} mHa)" if fci is not None else ""))
+    lines.append(f"selected CI stopped : {sci['stopped']}")
+    return lines
+
+
+def _summarise(opt, molecule, exp_name, eig_val, n_unq, train_time, exact=None, pt2=None, sci=None):
     """summary.txt next to the checkpoints (the reference's _base.py:330-390, same quantities)."""
     e = np.array([x[1] for x in opt.log[LogKey.E_LOC]])
     window = min(50, len(e))
@@ -358,6 +400,9 @@ def _summarise(opt, molecule, exp_name, eig_val, n_unq, train_time, exact=None, 
         lines.append(f"VMC energy with exact local energies: {exact['E']:.8f} ± {exact['stderr']:.2e} Ha "
                      f"({exact['n_unq']} sampled + {exact['n_connected']} connected states)")
         res.update(e_exact=exact["E"], e_exact_stderr=exact["stderr"])
+    if sci is not None:
+        lines.extend(_sci_lines(sci, fci))
+        res.update(sci_history=sci["history"], sci_extrapolated=sci["extrapolated"], sci_stopped=sci["stopped"])
     mk_dir(opt.save_loc, quiet=True)
     with open(os.path.join(opt.save_loc, "summary.txt"), "w") as f:
         f.write("\n".join(lines) + "\n")
@@ -464,6 +509,7 @@ def run_from_parser(parser, argv=None):
         raise ValueError("-sr_solver chooses the solver of -sr (natural gradient): give -sr as well")
     if args.sr_momentum and not args.sr:
         raise ValueError("-sr_momentum sets the momentum of -sr (natural gradient): give -sr as well")
+    _check_sci(args.sci, args.sci_grow, args.sci_start)
     if args.farm and "WORLD_SIZE" not in os.environ and (args.per_gpu > 1 or args.seeds or args.farm_gpus > 0):
         return _farm_launch(args, argv)
     rank, world = _setup_distributed(args.farm, args.per_gpu)
@@ -499,6 +545,8 @@ def _run_job(args, molecule_fname, seed):
             continue
         if (key == "sr_solver" and val is None) or (key == "sr_momentum" and not val):
             continue
+        if (key == "sci" and not val) or (key in ("sci_grow", "sci_start") and val is None):
+            continue
         print(f"\t{key} : {val}")
     print("")
     return _run(molecule_fname=molecule_fname, hamiltonian_fname=args.hamiltonian_fname, exp_name=exp_name,
@@ -516,7 +564,9 @@ def _run_job(args, molecule_fname, seed):
                 overwrite_pauli_hamiltonian=args.overwriteH, verbose=args.verbose, seed=seed, exact_eloc=args.exact_eloc,
                 train_exact_eloc=args.train_exact_eloc, **(dict(sr=True, sr_shift=args.sr_shift, sr_lr=args.sr_lr) if args.sr else {}),
                 **({} if args.sr_solver is None else dict(sr_solver=args.sr_solver)),
-                **(dict(sr_momentum=args.sr_momentum) if args.sr_momentum else {}), **(dict(pt2=True) if args.pt2 else {}))
+                **(dict(sr_momentum=args.sr_momentum) if args.sr_momentum else {}), **(dict(pt2=True) if args.pt2 else {}),
+                **(dict(sci=args.sci) if args.sci else {}), **({} if args.sci_grow is None else dict(sci_grow=args.sci_grow)),
+                **({} if args.sci_start is None else dict(sci_start=args.sci_start)))
 
 
 def run(*args, **kwargs):

@@ -38,6 +38,7 @@ class DevicePauliHamiltonian:
 
     def __init__(self, packed: PackedHamiltonian, device=None):
         self._h = ctypes.c_void_p(None)
+        self.last_lanczos_iterations = 0          # products of the most recent lowest_eigenpair call (measurement aid)
         self._lib = _lib.load_library()           # raises NaqsError when the HIP library is missing
         if not torch.cuda.is_available():
             raise _lib.NaqsError("DevicePauliHamiltonian needs a HIP device (no CPU fallback)")
@@ -217,15 +218,22 @@ class DevicePauliHamiltonian:
         return res[:, 0].contiguous() if real else res
 
     @torch.no_grad()
-    def lowest_eigenpair(self, keys, max_iter=400, tol=1e-10, seed=0):
+    def lowest_eigenpair(self, keys, max_iter=400, tol=1e-10, seed=0, v0=None):
         """Lowest eigenpair of H restricted to the sampled keys by Lanczos with full re-orthogonalisation, every
         product matrix-free on the device (no M x M or M x Kxy matrix is formed): the scalable form of the
-        sampled-subspace diagonalisation of solve_H (energy.py:762-786).  -> (eigenvalue, eigenvector float64 [M])."""
+        sampled-subspace diagonalisation of solve_H (energy.py:762-786).  -> (eigenvalue, eigenvector float64 [M]).
+        ``v0``: a start vector [M] (normalised here) in place of the seeded random one; ``None`` is the random start, bit for
+        bit.  ``last_lanczos_iterations`` holds the number of products the call took."""
         M = keys.shape[0]
         if M == 0:
             raise ValueError("empty sample set")
-        gen = torch.Generator(device=self.device).manual_seed(int(seed))
-        v = torch.randn(M, dtype=torch.float64, device=self.device, generator=gen)
+        if v0 is None:
+            gen = torch.Generator(device=self.device).manual_seed(int(seed))
+            v = torch.randn(M, dtype=torch.float64, device=self.device, generator=gen)
+        else:
+            v = v0.to(device=self.device, dtype=torch.float64).clone()
+            if v.shape != (M,) or not float(v.norm()) > 0:
+                raise ValueError(f"v0 must be a non-zero vector of shape [{M}]")
         v /= v.norm()
         m_max = int(min(max_iter, M))
         V = torch.empty((m_max, M), dtype=torch.float64, device=self.device)
@@ -258,6 +266,7 @@ class DevicePauliHamiltonian:
             v = w / b
         vec = torch.as_tensor(s_vec, dtype=torch.float64, device=self.device) @ V[:k + 1]
         vec = vec / vec.norm()
+        self.last_lanczos_iterations = k + 1
         return float(theta), vec
 
     # ---- Epstein-Nesbet second-order correction of a subspace energy -----------------------------
@@ -304,6 +313,80 @@ class DevicePauliHamiltonian:
         out4 = self.pt2(keys, vec, e0, ext).tolist()
         return dict(e0=float(e0), e_pt2=out4[0], n_external=int(n_ext), n_intruders=int(out4[2]), residual2=out4[1],
                     intruder_residual2=out4[3])
+
+    # ---- selected CI: the subspace grown by PT2 importance ------------------------------------------
+    # tie_rtol's default: on the committed fixtures symmetry partners (spin flip, spatial) have importances equal to <= 1e-13
+    # relative — rounding noise — while the smallest genuine gap met at a cut was 1.8e-4 relative; 1e-9 sits four orders above
+    # the one and five below the other, so a cut never orders partners by noise and never merges distinct groups.
+    def pt2_select(self, ext_keys, num, diag, e0, k, eps_min=0.0, tie_rtol=1e-9):
+        """``naqs_ham_pt2_select`` on the rows ``pt2(rows=True)`` returns: eps_a = num_a^2 / (diag_a - e0) (+inf for an intruder:
+        not diag_a - e0 > 0, or num_a NaN); eligible: eps > 0 and eps >= eps_min; with tau the k-th largest eligible eps, every
+        eligible row with eps >= tau (1 - tie_rtol) is selected — all eligible rows when k reaches their number, none when
+        k <= 0.  A near-degenerate group at the cut is taken whole, so the count may exceed k.
+
+        -> (selected keys in row order, int64 device tensor; number of intruders among them).  One read-back (the counts)."""
+        n_ext = ext_keys.shape[0]
+        if not (ext_keys.is_cuda and ext_keys.dtype == torch.int64):
+            raise ValueError("ext_keys must be an int64 device tensor")
+        num = num.to(device=self.device, dtype=torch.float64).contiguous()
+        diag = diag.to(device=self.device, dtype=torch.float64).contiguous()
+        if num.shape != (n_ext,) or diag.shape != (n_ext,):
+            raise ValueError(f"num and diag must have shape [{n_ext}]")
+        ext_keys = ext_keys.contiguous()
+        out = torch.empty(n_ext, dtype=torch.int64, device=self.device)
+        count = torch.empty(2, dtype=torch.int64, device=self.device)
+        st = self._lib.naqs_ham_pt2_select(self._h, n_ext, ext_keys.data_ptr() if n_ext else None, num.data_ptr() if n_ext else None,
+                                           diag.data_ptr() if n_ext else None, float(e0), int(k), float(eps_min), float(tie_rtol),
+                                           n_ext, out.data_ptr() if n_ext else None, count.data_ptr(), _stream_ptr(self.device))
+        _lib.check(st, "naqs_ham_pt2_select")
+        n_sel, n_intr = count.tolist()
+        return out[:n_sel], int(n_intr)
+
+    @torch.no_grad()
+    def selected_ci(self, keys, n_add, eps_min=0.0, tie_rtol=1e-9, max_states=1 << 20, max_external=1 << 27, tol=1e-10):
+        """Selected CI from the subspace ``keys`` (int64 device tensor, unique): diagonalise, measure every connected state's
+        second-order importance, move the most important ones into the subspace, diagonalise again.
+
+        ``n_add``: a sequence of ints — k of each growth step, so len(n_add) + 1 iterations — or ``(n_iter, grow)`` with a
+        float ``grow``: n_iter iterations, k = ceil(grow M) at each growth step.  Iteration t: Lanczos on S_t (the first from
+        lowest_eigenpair's own random start, as solve_H; later ones from (c_{t-1}, 0)), ``connected_keys``, ``pt2(rows=True)``,
+        the record, and — unless it is the last — ``pt2_select`` and S_{t+1} = cat(S_t, selected).  Every E_S is variational
+        and the subspaces are nested, so E_S never rises; E_S + E_PT2 is not variational.
+
+        -> dict(keys, vec, history=[dict(M, e0, e_pt2, n_external, n_intruders, n_added)], stopped, extrapolated);
+        ``stopped``: "schedule" (all iterations done), "connected set empty", "nothing eligible" or "max_states"."""
+        ks, grow = _sci_schedule(n_add)
+        n_iter = len(ks) + 1 if grow is None else ks
+        keys = keys.contiguous()
+        history, vec, stopped = [], None, "schedule"
+        for t in range(n_iter):
+            M = keys.shape[0]
+            e0, vec = self.lowest_eigenpair(keys, tol=tol, v0=vec)
+            capacity = self.connected_capacity(M, M)
+            if capacity > max_external:
+                raise ValueError(f"the connected set of {M} keys may hold {capacity} keys, more than max_external = {max_external}")
+            ext, n_ext = self.connected_keys(keys, capacity=capacity)
+            out4, num, diag = self.pt2(keys, vec, e0, ext, rows=True)
+            out4 = out4.tolist()
+            rec = dict(M=M, e0=float(e0), e_pt2=out4[0], n_external=int(n_ext), n_intruders=int(out4[2]), n_added=0)
+            history.append(rec)
+            if n_ext == 0:
+                stopped = "connected set empty"
+                break
+            if t == n_iter - 1:
+                break
+            k = int(ks[t]) if grow is None else int(np.ceil(grow * M))
+            sel, _ = self.pt2_select(ext, num, diag, e0, k, eps_min=eps_min, tie_rtol=tie_rtol)
+            if sel.shape[0] == 0:
+                stopped = "nothing eligible"
+                break
+            if M + sel.shape[0] > max_states:
+                stopped = "max_states"
+                break
+            rec["n_added"] = int(sel.shape[0])
+            keys = torch.cat([keys, sel])
+            vec = torch.cat([vec, torch.zeros(sel.shape[0], dtype=torch.float64, device=self.device)])
+        return dict(keys=keys, vec=vec, history=history, stopped=stopped, extrapolated=extrapolate_pt2(history))
 
     # ---- inner ring ----------------------------------------------------------------------------
     def dense_hij(self, keys):
@@ -416,3 +499,26 @@ class MatrixFreePauliHamiltonian(DevicePauliHamiltonian):
         rows = np.broadcast_to(np.arange(len(k))[:, None], j.shape)[hit]
         cols = order[pos[hit]]
         return csr_matrix((hij[hit], (rows, cols)), shape=(len(k), len(k)))
+
+
+def _sci_schedule(n_add):
+    """``selected_ci``'s n_add -> (list of k, None) or (n_iter, grow)."""
+    n_add = tuple(n_add)
+    if len(n_add) == 2 and isinstance(n_add[1], float):
+        n_iter, grow = int(n_add[0]), float(n_add[1])
+        if n_iter < 1 or not grow > 0:
+            raise ValueError(f"n_add = (n_iter, grow) needs n_iter >= 1 and grow > 0, got {n_add}")
+        return n_iter, grow
+    if any(int(k) != k for k in n_add):
+        raise ValueError(f"n_add must be a sequence of ints or (n_iter, grow) with a float grow, got {n_add}")
+    return [int(k) for k in n_add], None
+
+
+def extrapolate_pt2(history, n_fit=3):
+    """The intercept at E_PT2 = 0 of the least-squares line of e0 against e_pt2 over the last ``n_fit`` (>= 3) iterations of
+    ``selected_ci`` with e_pt2 < 0; None with fewer than three of them.  Not variational."""
+    pts = [(h["e_pt2"], h["e0"]) for h in history if h["e_pt2"] < 0][-max(3, int(n_fit)):]
+    if len(pts) < 3:
+        return None
+    x, y = np.array(pts).T
+    return float(np.polyfit(x, y, 1)[1])

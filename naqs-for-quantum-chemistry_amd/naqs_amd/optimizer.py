@@ -1208,17 +1208,19 @@ class PartialSamplingOptimizer(OptimizerBase):
             return self.get_samples(action, lazy=lazy)
         return states, counts, probs
 
-    def _solve_H_keys(self, n_samps):
-        """The sample of solve_H: one draw from the optimiser's generator, cut to the solve_H_max_states most frequent
-        states.  -> (keys, unique states drawn)"""
+    def _solve_H_keys(self, n_samps, limit=None):
+        """The sample of solve_H: one draw from the optimiser's generator, cut to the ``limit`` (default: solve_H_max_states)
+        most frequent states.  -> (keys, unique states drawn)"""
         if n_samps is None:
             n_samps = self.get_n_samples()
         with torch.no_grad():
             states, counts, probs = self.wavefunction.sample(n_samps, ret_log_psi=False, generator=self.generator)
         n_unq = len(states)
-        limit = self.solve_H_max_states
+        said = limit is None                      # solve_H's own cap announces itself; a caller's limit is the caller's business
+        limit = self.solve_H_max_states if limit is None else limit
         if n_unq > limit:
-            print(f"Limiting number of sampled states from {n_unq} is to most likely {limit}.")
+            if said:
+                print(f"Limiting number of sampled states from {n_unq} is to most likely {limit}.")
             states = states[torch.argsort(counts)[-limit:]]
         return self.hilbert.state2idx(states).squeeze(-1), n_unq
 
@@ -1259,6 +1261,18 @@ class PartialSamplingOptimizer(OptimizerBase):
         pt2 = self.pauli_hamiltonian.pt2_correction(keys_dev, vec, e0=val)
         return dict(eig=val, vec0=abs(float(vec[0])), n_unq=n_unq, e_pt2=pt2["e_pt2"], n_external=pt2["n_external"],
                     n_intruders=pt2["n_intruders"])
+
+    def solve_H_sci(self, n_samps=None, n_iter=4, grow=1.0, n_start=None, **kwargs):
+        """Selected CI from solve_H's sample (DevicePauliHamiltonian.selected_ci): ``n_iter`` iterations, each growth step
+        adding the ceil(grow M) connected states of largest second-order importance.  ``n_start`` cuts the draw to its
+        n_start most frequent states first.  Iteration 0 is solve_H_pt2 on the same draw, bit for bit.
+        -> selected_ci's dict, plus n_unq (unique states drawn).  Device only."""
+        if self.device.type != "cuda":
+            raise NotImplementedError("solve_H_sci runs on the HIP kernels (naqs_ham_pt2_select): there is no CPU form")
+        keys, n_unq = self._solve_H_keys(n_samps, limit=None if n_start is None else min(self.solve_H_max_states, int(n_start)))
+        res = self.pauli_hamiltonian.selected_ci(keys_to_device(keys, self.device), (int(n_iter), float(grow)), **kwargs)
+        res["n_unq"] = n_unq
+        return res
 
     def run(self, n_epochs, save_freq=None, save_final=False, reset_log=False, reset_optimizer=False,
             output_freq=50):
