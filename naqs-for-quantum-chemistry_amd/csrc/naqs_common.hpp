@@ -52,6 +52,20 @@ inline int env_int(const char *name, int dflt) {
     return v ? std::atoi(v) : dflt;
 }
 
+// A handle's scratch array that grows on demand and never shrinks: wait for the device (a launch in flight, on any stream, may
+// still read the old array), free it, allocate `bytes` for `new_cap` entries, record the capacity (0 while there is no array).
+// head_room: the capacity asked for n entries, a quarter more, so that a slowly growing n does not come back every call.
+inline int64_t head_room(int64_t n, int64_t least) { return n + n / 4 > least ? n + n / 4 : least; }
+template <typename T>
+inline int regrow(T *&ptr, int64_t &cap, int64_t new_cap, size_t bytes) {
+    HIP_TRY(hipDeviceSynchronize());
+    if (ptr) (void)hipFree(ptr);
+    ptr = nullptr; cap = 0;
+    HIP_TRY(hipMalloc((void **)&ptr, bytes));
+    cap = new_cap;
+    return NAQS_OK;
+}
+
 // HIP-event pairs around the launches of one kernel (bench.py's roofline leg)
 struct EventRing {
     hipEvent_t *ev = nullptr;

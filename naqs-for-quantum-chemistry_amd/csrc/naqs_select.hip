@@ -361,12 +361,9 @@ NAQS_API int naqs_ham_pt2_select(naqs_ham_t *h, int64_t n_ext, const uint64_t *e
         const int64_t n_wg = (n_ext + MULTI_TILE - 1) / MULTI_TILE;
         SelectScratch *sc = ham_select_scratch(h);
         if (n_wg > sc->tiles) {
-            HIP_TRY(hipDeviceSynchronize());
-            if (sc->words) (void)hipFree(sc->words);
-            sc->words = nullptr; sc->tiles = 0;
-            const int64_t cap = std::max<int64_t>(64, n_wg + n_wg / 4);
-            HIP_TRY(hipMalloc((void **)&sc->words, ((size_t)HIST_WORDS + 3 * (size_t)cap) * sizeof(uint32_t)));
-            sc->tiles = cap;
+            const int64_t cap = head_room(n_wg, 64);
+            st = regrow(sc->words, sc->tiles, cap, ((size_t)HIST_WORDS + 3 * (size_t)cap) * sizeof(uint32_t));
+            if (st != NAQS_OK) return st;
         }
         uint32_t *ghist = sc->words, *wg_cnt = ghist + HIST_WORDS, *wg_intr = wg_cnt + sc->tiles, *wg_off = wg_intr + sc->tiles;
         HIP_TRY(hipMemsetAsync(ghist, 0, HIST_WORDS * sizeof(uint32_t), s));
