@@ -221,6 +221,47 @@ int naqs_ham_pt2_select(naqs_ham_t *h, int64_t n_ext, const uint64_t *ext_keys_d
                         const double *diag_dev, double e0, int64_t k, double eps_min, double tie_rtol,
                         int64_t capacity, uint64_t *out_keys_dev, int64_t *count_dev /* [2] */, void *stream);
 
+/*
+ * The lowest eigenpair of H restricted to the M table keys keys_dev (unique, physical, any order), by a diagonally
+ * preconditioned Davidson iteration in real float64.  H on the table must be symmetric; d_i = H_ii; v0_dev[M] is the start.
+ *
+ *   v_0 = v0 / |v0| ;  w_0 = H v_0 ;  m = 1 ;  products = 1
+ *   repeat
+ *       G_kl = v_k . w_l  (k <= l, mirrored)            m x m
+ *       (theta, s) = lowest eigenpair of G, |s| = 1
+ *       x = sum_k s_k v_k ;  y = sum_k s_k w_k ;  r = y - theta x ;  rho = |r|
+ *       rho < tol * max(1, |theta|)            -> status 0 (converged)
+ *       m == M                                 -> status 2 (the basis spans the space; the pair is exact to rounding)
+ *       products == max_products               -> status 1 (not converged; the pair is still returned)
+ *       t_i = -r_i / max(d_i - theta, delta)
+ *       m == m_max: restart                    V <- [x / |x|], W <- [y / |x|], m = 1
+ *       twice:  t <- t - V (V^T t)
+ *       |t| not finite, or <= 1e-14 * its norm before the two passes   -> status 3 (breakdown)
+ *       v_m = t / |t| ;  w_m = H v_m ;  m += 1 ;  products += 1
+ *   return theta, x / |x|, rho, products, status
+ *
+ * The correction is the positive-definite one: r / (theta - d), the textbook form, is a Newton step towards the eigenvalue
+ * nearest theta and converges to excited states from a random start; with the denominator held at or above delta the step
+ * always descends, and the iteration finds the lowest state of what v0 overlaps (a start that is an exact eigenvector is a
+ * stationary point and is returned as such).
+ * The product is the row walk of naqs_ham_pt2 over the table's own keys: H v = num + d * v, the key table built once per call.
+ * The device forms w_m = (H t) / |t| where the rule writes H (t / |t|), the restart keeps x and y without the division by
+ * |x| = 1 + O(2^-52), and G_00 after a restart is theta: each differs from the rule by roundings only.  The m x m problem is
+ * solved by cyclic Jacobi in float64 in one workgroup.  Every sum over M runs in one fixed order (per-tile partial sums
+ * combined in tile order, no floating-point atomics): the same inputs give the same bits on repetition, whatever the form of
+ * the row walk's kernel.
+ * vec_dev[M] receives x / |x|; info_host[4] (host memory) theta, rho, products, status.  The call synchronises the stream once
+ * per product (eight words are read back) and once before the first.  Scratch — (2 m_max + 4) vectors of M doubles — belongs
+ * to the handle and grows on demand behind a device synchronisation.  naqs_ham_last_kernel names the row walk's kernel and
+ * the solver's.
+ * NAQS_ERR_INVALID: M < 1, a null pointer, tol or delta not positive and finite, m_max outside 2 .. 32, max_products < 1, or a
+ * zero or non-finite v0 (found on the device; no product is run and vec_dev is untouched).  NAQS_ERR_UNSUPPORTED: M > 2^24 - 1
+ * (as naqs_ham_pt2).  It stands in for no reference code (the reference diagonalises the subspace with SciPy on the host).
+ */
+int naqs_ham_eig_lowest(naqs_ham_t *h, int64_t M, const uint64_t *keys_dev, const double *v0_dev, double tol,
+                        int32_t max_products, int32_t m_max, double delta, double *vec_dev /* [M] */,
+                        double info_host[4] /* theta, rho, products, status */, void *stream);
+
 /* ---- inner ring: device versions of the three Cython entry points the reference imports ---- */
 
 /* src.utils.hamiltonian_math.popcount_parity (hamiltonian_math.pyx:455-484):

@@ -60,6 +60,9 @@ _VALUE_FLAGS = [
                                           "moves the connected states of largest second-order importance into it (0: off).")),
     (("-sci_grow",), "sci_grow", dict(type=float, help="Selected CI: states added per growth step, as a fraction of the subspace (1.0).")),
     (("-sci_start",), "sci_start", dict(type=int, help="Selected CI: start from the n most frequent sampled states (all of them).")),
+    (("-eig_solver",), "eig_solver", dict(type=str, choices=["lanczos", "davidson"],
+                                          help="The sampled-subspace diagonalisations (also -pt2's and -sci's) by Lanczos (the default) or by "
+                                               "the Davidson solver of naqs_ham_eig_lowest.")),
 ]
 # (flags, dest, default expression on the get_parser keywords, help)
 _SWITCHES = [
@@ -93,7 +96,8 @@ _DEFAULTS = dict(molecule="molecules/H2", hamiltonian_fname=None, out=None, numb
                  pretrained_model_loc=None, cont=False, n_excitations_max=-1, comb_amp_phase=False,
                  use_amp_spin_sym=True, use_phase_spin_sym=False, aggregate_phase=True, restrict_H=True,
                  reset_opt=False, verbose=False, seed=-1, exact_eloc=False, train_exact_eloc=False,
-                 sr=False, sr_shift=1e-3, sr_lr=0.1, sr_solver=None, sr_momentum=0.0, pt2=False, sci=0, sci_grow=None, sci_start=None)
+                 sr=False, sr_shift=1e-3, sr_lr=0.1, sr_solver=None, sr_momentum=0.0, pt2=False, sci=0, sci_grow=None, sci_start=None,
+                 eig_solver=None)
 
 
 def get_parser(**overrides):
@@ -192,7 +196,7 @@ def _run(molecule_fname, hamiltonian_fname, exp_name, num_experiments, pretraine
          n_layer_phase, n_excitations_max, comb_amp_phase, use_amp_spin_sym, use_phase_spin_sym, aggregate_phase,
          use_restrictedH, loadH, presolveH, overwrite_pauli_hamiltonian, verbose, seed, device=None, exact_eloc=False,
          train_exact_eloc=False, sr=False, sr_shift=1e-3, sr_lr=0.1, sr_solver=None, sr_momentum=0.0, pt2=False,
-         sci=0, sci_grow=None, sci_start=None):
+         sci=0, sci_grow=None, sci_start=None, eig_solver=None):
     _check_sci(sci, sci_grow, sci_start)
     if sr_solver is not None and not sr:
         raise ValueError("-sr_solver chooses the solver of -sr (natural gradient): give -sr as well")
@@ -223,7 +227,8 @@ def _run(molecule_fname, hamiltonian_fname, exp_name, num_experiments, pretraine
                            use_restrictedH, presolveH, verbose, seed, device, exact_eloc, train_exact_eloc,
                            dict(dict(diag_shift=sr_shift, lr=sr_lr), **({} if sr_solver is None else dict(solver=sr_solver)),
                                 **(dict(momentum=sr_momentum) if sr_momentum else {})) if sr else None, **(dict(pt2=True) if pt2 else {}),
-                           **(dict(sci=dict(n_iter=int(sci), grow=1.0 if sci_grow is None else float(sci_grow), n_start=sci_start)) if sci else {}))
+                           **(dict(sci=dict(n_iter=int(sci), grow=1.0 if sci_grow is None else float(sci_grow), n_start=sci_start)) if sci else {}),
+                           **({} if eig_solver is None else dict(eig_solver=eig_solver)))
     finally:
         if locked[0]:
             _SETUP_LOCK.release()
@@ -236,7 +241,7 @@ def _run_locked(locked, molecule_fname, hamiltonian_fname, exp_name, num_experim
                 reset_optimizer, qubit_ordering, masking, lr, lr_lut, n_samps, n_samps_max, n_unq_samps_min, n_unq_samps_max,
                 n_train, n_pretrain, output_freq, save_freq, n_lut, n_hid, n_layer, n_hid_phase, n_layer_phase, comb_amp_phase,
                 use_amp_spin_sym, use_phase_spin_sym, aggregate_phase, use_restrictedH, presolveH, verbose, seed, device,
-                exact_eloc=False, train_exact_eloc=False, natural_gradient=None, pt2=False, sci=None):
+                exact_eloc=False, train_exact_eloc=False, natural_gradient=None, pt2=False, sci=None, eig_solver=None):
     seed = set_global_seed(_agree_on_seed(seed))
     molecule, qubit_hamiltonian = load_molecule(molecule_fname, hamiltonian_fname=hamiltonian_fname, verbose=True)
     N = molecule.n_qubits
@@ -289,7 +294,8 @@ def _run_locked(locked, molecule_fname, hamiltonian_fname, exp_name, num_experim
             optimizer_args=[{'lr': lr, 'betas': (0.9, 0.99), 'weight_decay': 0, 'eps': 1e-15, 'amsgrad': False},
                             {'lr': lr_lut}],
             save_loc=exp_name_i, pauli_hamiltonian_dtype=np.float64, verbose=verbose, seed=seed + i,
-            exact_local_energies=train_exact_eloc, **({"natural_gradient": natural_gradient} if natural_gradient else {}))
+            exact_local_energies=train_exact_eloc, **({"natural_gradient": natural_gradient} if natural_gradient else {}),
+            **({} if eig_solver is None else {"eig_solver": eig_solver}))
         print("\n---System summary---\n")
         print(f"Size of restricted subspace : {hilbert.size}.")
         print("Qubit ordering in model :", wavefunction.qubit2model_permutation)
@@ -545,7 +551,7 @@ def _run_job(args, molecule_fname, seed):
             continue
         if (key == "sr_solver" and val is None) or (key == "sr_momentum" and not val):
             continue
-        if (key == "sci" and not val) or (key in ("sci_grow", "sci_start") and val is None):
+        if (key == "sci" and not val) or (key in ("sci_grow", "sci_start", "eig_solver") and val is None):
             continue
         print(f"\t{key} : {val}")
     print("")
@@ -566,7 +572,8 @@ def _run_job(args, molecule_fname, seed):
                 **({} if args.sr_solver is None else dict(sr_solver=args.sr_solver)),
                 **(dict(sr_momentum=args.sr_momentum) if args.sr_momentum else {}), **(dict(pt2=True) if args.pt2 else {}),
                 **(dict(sci=args.sci) if args.sci else {}), **({} if args.sci_grow is None else dict(sci_grow=args.sci_grow)),
-                **({} if args.sci_start is None else dict(sci_start=args.sci_start)))
+                **({} if args.sci_start is None else dict(sci_start=args.sci_start)),
+                **({} if args.eig_solver is None else dict(eig_solver=args.eig_solver)))
 
 
 def run(*args, **kwargs):

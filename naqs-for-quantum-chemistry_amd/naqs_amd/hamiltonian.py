@@ -39,6 +39,7 @@ class DevicePauliHamiltonian:
     def __init__(self, packed: PackedHamiltonian, device=None):
         self._h = ctypes.c_void_p(None)
         self.last_lanczos_iterations = 0          # products of the most recent lowest_eigenpair call (measurement aid)
+        self.last_eig_info = None                 # dict(products, residual, status) of the most recent solver="davidson" call
         self._lib = _lib.load_library()           # raises NaqsError when the HIP library is missing
         if not torch.cuda.is_available():
             raise _lib.NaqsError("DevicePauliHamiltonian needs a HIP device (no CPU fallback)")
@@ -218,15 +219,24 @@ class DevicePauliHamiltonian:
         return res[:, 0].contiguous() if real else res
 
     @torch.no_grad()
-    def lowest_eigenpair(self, keys, max_iter=400, tol=1e-10, seed=0, v0=None):
+    def lowest_eigenpair(self, keys, max_iter=400, tol=1e-10, seed=0, v0=None, solver="lanczos", m_max=16, delta=1e-2):
         """Lowest eigenpair of H restricted to the sampled keys by Lanczos with full re-orthogonalisation, every
         product matrix-free on the device (no M x M or M x Kxy matrix is formed): the scalable form of the
         sampled-subspace diagonalisation of solve_H (energy.py:762-786).  -> (eigenvalue, eigenvector float64 [M]).
         ``v0``: a start vector [M] (normalised here) in place of the seeded random one; ``None`` is the random start, bit for
-        bit.  ``last_lanczos_iterations`` holds the number of products the call took."""
+        bit.  ``last_lanczos_iterations`` holds the number of products the call took.
+
+        ``solver="davidson"``: the diagonally preconditioned Davidson iteration of the library (``naqs_ham_eig_lowest``) from
+        the same start — ``max_iter`` bounds its products, ``m_max`` (2..32) its basis, ``delta`` floors the preconditioner —
+        and ``last_eig_info = dict(products, residual, status)`` (status 0 converged, 1 ``max_iter`` reached, 2 the basis spans
+        the space, 3 breakdown).  H on the keys must be symmetric."""
+        if solver not in ("lanczos", "davidson"):
+            raise ValueError(f"solver must be 'lanczos' or 'davidson', got {solver!r}")
         M = keys.shape[0]
         if M == 0:
             raise ValueError("empty sample set")
+        if solver == "davidson":
+            return self._davidson(keys, int(max_iter), float(tol), seed, v0, int(m_max), float(delta))
         if v0 is None:
             gen = torch.Generator(device=self.device).manual_seed(int(seed))
             v = torch.randn(M, dtype=torch.float64, device=self.device, generator=gen)
@@ -268,6 +278,33 @@ class DevicePauliHamiltonian:
         vec = vec / vec.norm()
         self.last_lanczos_iterations = k + 1
         return float(theta), vec
+
+    def _davidson(self, keys, max_iter, tol, seed, v0, m_max, delta):
+        M = keys.shape[0]
+        if not (keys.is_cuda and keys.dtype == torch.int64):
+            raise ValueError("keys must be an int64 device tensor")
+        if not 2 <= m_max <= 32:
+            raise ValueError(f"m_max must lie in 2..32, got {m_max}")
+        if max_iter < 1 or not (np.isfinite(tol) and tol > 0 and np.isfinite(delta) and delta > 0):
+            raise ValueError("max_iter must be at least 1, tol and delta positive and finite")
+        if v0 is None:
+            gen = torch.Generator(device=self.device).manual_seed(int(seed))
+            v = torch.randn(M, dtype=torch.float64, device=self.device, generator=gen)
+        else:
+            v = v0.to(device=self.device, dtype=torch.float64).contiguous()
+            if v.shape != (M,):
+                raise ValueError(f"v0 must be a non-zero vector of shape [{M}]")
+        keys = keys.contiguous()
+        vec = torch.empty(M, dtype=torch.float64, device=self.device)
+        info = (ctypes.c_double * 4)()
+        st = self._lib.naqs_ham_eig_lowest(self._h, M, keys.data_ptr(), v.data_ptr(), tol, max_iter, m_max, delta, vec.data_ptr(),
+                                           info, _stream_ptr(self.device))
+        if st == -1:                              # NAQS_ERR_INVALID: every other argument was checked above
+            raise ValueError(f"v0 must be a non-zero finite vector of shape [{M}]")
+        _lib.check(st, "naqs_ham_eig_lowest")
+        self.last_lanczos_iterations = int(info[2])
+        self.last_eig_info = dict(products=int(info[2]), residual=float(info[1]), status=int(info[3]))
+        return float(info[0]), vec
 
     # ---- Epstein-Nesbet second-order correction of a subspace energy -----------------------------
     def pt2(self, keys, c, e0, ext_keys, rows=False):
@@ -343,7 +380,8 @@ class DevicePauliHamiltonian:
         return out[:n_sel], int(n_intr)
 
     @torch.no_grad()
-    def selected_ci(self, keys, n_add, eps_min=0.0, tie_rtol=1e-9, max_states=1 << 20, max_external=1 << 27, tol=1e-10):
+    def selected_ci(self, keys, n_add, eps_min=0.0, tie_rtol=1e-9, max_states=1 << 20, max_external=1 << 27, tol=1e-10,
+                    solver="lanczos"):
         """Selected CI from the subspace ``keys`` (int64 device tensor, unique): diagonalise, measure every connected state's
         second-order importance, move the most important ones into the subspace, diagonalise again.
 
@@ -353,6 +391,8 @@ class DevicePauliHamiltonian:
         the record, and — unless it is the last — ``pt2_select`` and S_{t+1} = cat(S_t, selected).  Every E_S is variational
         and the subspaces are nested, so E_S never rises; E_S + E_PT2 is not variational.
 
+        ``solver``: lowest_eigenpair's ("lanczos" or "davidson"), for every iteration.
+
         -> dict(keys, vec, history=[dict(M, e0, e_pt2, n_external, n_intruders, n_added)], stopped, extrapolated);
         ``stopped``: "schedule" (all iterations done), "connected set empty", "nothing eligible" or "max_states"."""
         ks, grow = _sci_schedule(n_add)
@@ -361,7 +401,7 @@ class DevicePauliHamiltonian:
         history, vec, stopped = [], None, "schedule"
         for t in range(n_iter):
             M = keys.shape[0]
-            e0, vec = self.lowest_eigenpair(keys, tol=tol, v0=vec)
+            e0, vec = self.lowest_eigenpair(keys, tol=tol, v0=vec, solver=solver)
             capacity = self.connected_capacity(M, M)
             if capacity > max_external:
                 raise ValueError(f"the connected set of {M} keys may hold {capacity} keys, more than max_external = {max_external}")

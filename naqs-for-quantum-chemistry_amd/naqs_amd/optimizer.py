@@ -932,7 +932,11 @@ class PartialSamplingOptimizer(OptimizerBase):
     """Optimise with partial sampling of the Hilbert space (energy.py:731-1056)."""
 
     def __init__(self, n_samples, n_samples_max=1e9, n_unq_samples_min=1000, n_unq_samples_max=1e6,
-                 log_exact_energy=True, exact_local_energies=False, natural_gradient=None, **kwargs):
+                 log_exact_energy=True, exact_local_energies=False, natural_gradient=None, eig_solver="lanczos", **kwargs):
+        # eig_solver: lowest_eigenpair's solver for the sampled-subspace diagonalisations (solve_H, solve_H_pt2, solve_H_sci)
+        if eig_solver not in ("lanczos", "davidson"):
+            raise ValueError(f"eig_solver must be 'lanczos' or 'davidson', got {eig_solver!r}")
+        self.eig_solver = eig_solver
         # natural_gradient: None (Adam, as always) or dict(diag_shift=..., lr=...[, solver="torch" | "hip"]): stochastic
         # reconfiguration in sample space (minSR) on the Gram kernels of naqs_sr.hip; the optimiser passed in optimizer= is then
         # never stepped.  solver: who solves the two systems — torch's Cholesky (the default) or naqs_net_sr_solve.  momentum: SPRING's
@@ -1228,7 +1232,7 @@ class PartialSamplingOptimizer(OptimizerBase):
         """Matrix-free Lanczos on the device: no sub-matrix is formed, so the reference's 10 000-state cap (there for the
         cost of the CSR slice) is only kept as the default of solve_H_max_states.  -> (eigenvalue, device vector, device keys)"""
         keys_dev = keys_to_device(keys, self.device)
-        val, vec = self.pauli_hamiltonian.lowest_eigenpair(keys_dev)
+        val, vec = self.pauli_hamiltonian.lowest_eigenpair(keys_dev, solver=self.eig_solver)
         return float(val), vec, keys_dev
 
     def solve_H(self, n_samps=None, ret_n_samps=True):
@@ -1270,6 +1274,7 @@ class PartialSamplingOptimizer(OptimizerBase):
         if self.device.type != "cuda":
             raise NotImplementedError("solve_H_sci runs on the HIP kernels (naqs_ham_pt2_select): there is no CPU form")
         keys, n_unq = self._solve_H_keys(n_samps, limit=None if n_start is None else min(self.solve_H_max_states, int(n_start)))
+        kwargs.setdefault("solver", self.eig_solver)
         res = self.pauli_hamiltonian.selected_ci(keys_to_device(keys, self.device), (int(n_iter), float(grow)), **kwargs)
         res["n_unq"] = n_unq
         return res
