@@ -63,6 +63,11 @@ def _accumulate(p, grad):
         p.grad.add_(grad)
 
 
+def _seed64(seed):
+    """A Python seed as the uint64 the library takes."""
+    return int(seed) & (2 ** 64 - 1)
+
+
 class FusedLogPsi:
     def __init__(self, wavefunction):
         wf, m = wavefunction, wavefunction.model
@@ -166,6 +171,48 @@ class FusedLogPsi:
         _lib.check(fn(self._h, flat.data_ptr(), flat.numel(), _stream_ptr(self.device)), "naqs_net_set_weights")
         self._flat = flat          # keep alive until the async copy has been consumed
 
+    # ---- what the training calls share: the flat gradient, the one-call step's outputs, FlatAdam's arguments ----
+    def _ensure_grad_flat(self):
+        """The persistent flat gradient buffer the backward kernels write (float32 [n_params], state_dict order) and its
+        per-parameter views, both made once.  -> the buffer"""
+        if self._grad_flat is None:
+            self._grad_flat = torch.empty(self.n_params, dtype=torch.float32, device=self.device)
+            self._grad_views, off = [], 0
+            for p in self.wf.param_list():
+                n = p.numel()
+                self._grad_views.append(self._grad_flat[off:off + n].view(p.shape))
+                off += n
+        return self._grad_flat
+
+    def _table_buffers(self, cap):
+        """The cap-sized outputs of ``vmc_step`` / ``vmc_run`` live in per-handle buffers (allocated once per cap: eight
+        allocator calls per step were ~15 us of host time on a 0.2 ms step); they are valid until the next step of this
+        handle.  -> (counts, probs, weights, log psi, E_loc, g)"""
+        ob = getattr(self, "_onecall_bufs", None)
+        if ob is None or ob[0] != cap:
+            dev = self.device
+            ob = self._onecall_bufs = (cap, torch.empty(cap, dtype=torch.int64, device=dev), torch.empty(cap, dtype=torch.float32, device=dev),
+                                       torch.empty(cap, dtype=torch.float64, device=dev), torch.empty((cap, 2), dtype=torch.float32, device=dev),
+                                       torch.empty((cap, 2), dtype=torch.float64, device=dev), torch.empty((cap, 2), dtype=torch.float32, device=dev))
+        return ob[1:]
+
+    def _adam_args(self, adam, who):
+        """A ``FlatAdam`` on this network's flat vector as the library takes it: -> ((parameters, exp_avg, exp_avg_sq) pointers,
+        (lr, beta1, beta2, eps, weight_decay), the number of its next step)."""
+        if adam._flat.numel() != self.n_params:
+            raise ValueError(f"{who}: the optimiser's flat vector is not this network's")
+        grp = next(g_ for g_ in adam.param_groups if g_['params'])
+        hyper = (float(grp['lr']), float(grp['betas'][0]), float(grp['betas'][1]), float(grp['eps']), float(grp['weight_decay']))
+        return (adam._flat.data_ptr(), adam._m.data_ptr(), adam._v.data_ptr()), hyper, adam._t + 1
+
+    def _adam_stepped(self, adam, t):
+        """The library applied step ``t`` of ``adam`` and re-packed the weights from its flat vector."""
+        if not adam.state:
+            adam._bind_state()
+        adam._t = t
+        adam._opt_called = True          # (what torch's LR schedulers look at to see that a step preceded theirs)
+        self._flat = adam._flat
+
     def log_psi_train(self, keys):
         """Differentiable log psi [M, 2] of int64 device keys: amplitude blocks through the HIP forward/backward
         pair, the phase MLP (three Linear layers) through PyTorch/rocBLAS.  Same function of the parameters as
@@ -258,17 +305,11 @@ class FusedLogPsi:
             g, ev = self.vmc_loss_grad(e_loc, weights, sums, with_energy=True)
             self.backward_saved(saved, g)
             return g, ev
-        if self._grad_flat is None:
-            self._grad_flat = torch.empty(self.n_params, dtype=torch.float32, device=self.device)
-            self._grad_views, off = [], 0
-            for p in params:
-                n = p.numel()
-                self._grad_views.append(self._grad_flat[off:off + n].view(p.shape))
-                off += n
+        flat = self._ensure_grad_flat()
         g = torch.empty((M, 2), dtype=torch.float32, device=self.device)
         ev = torch.empty(2, dtype=torch.float64, device=self.device)
         st = self._lib.naqs_net_train_backward_vmc(self._h, M, keys.data_ptr(), e_loc.data_ptr(), weights.data_ptr(), sums.data_ptr(),
-                                                   g.data_ptr(), ev.data_ptr(), self._grad_flat.data_ptr(), _stream_ptr(self.device))
+                                                   g.data_ptr(), ev.data_ptr(), flat.data_ptr(), _stream_ptr(self.device))
         _lib.check(st, "naqs_net_train_backward_vmc")
         for p, gv in zip(params, self._grad_views):
             p.grad = gv
@@ -286,19 +327,9 @@ class FusedLogPsi:
             g = g.contiguous()
             params = self.wf.param_list()
             fresh = all(p.grad is None for p in params)
-            if fresh:
-                # the usual case (zero_grad before every step): the kernels write straight into a persistent flat
-                # buffer whose per-parameter views were made once
-                if self._grad_flat is None:
-                    self._grad_flat = torch.empty(self.n_params, dtype=torch.float32, device=self.device)
-                    self._grad_views, off = [], 0
-                    for p in params:
-                        n = p.numel()
-                        self._grad_views.append(self._grad_flat[off:off + n].view(p.shape))
-                        off += n
-                flat = self._grad_flat
-            else:
-                flat = torch.empty(self.n_params, dtype=torch.float32, device=self.device)
+            # the usual case (zero_grad before every step): the kernels write straight into the persistent flat buffer
+            flat = (self._ensure_grad_flat() if fresh
+                    else torch.empty(self.n_params, dtype=torch.float32, device=self.device))
             st = self._lib.naqs_net_train_backward(self._h, keys.shape[0], keys.data_ptr(), g.data_ptr(), flat.data_ptr(),
                                                    _stream_ptr(self.device))
             _lib.check(st, "naqs_net_train_backward")
@@ -479,11 +510,11 @@ class FusedLogPsi:
         info = self._samp
         if with_weights:
             weights = torch.empty(cap, dtype=torch.float64, device=self.device)
-            st = self._lib.naqs_net_sample_weighted(self._h, int(n_samples), int(seed) & (2 ** 64 - 1), cap, keys.data_ptr(),
+            st = self._lib.naqs_net_sample_weighted(self._h, int(n_samples), _seed64(seed), cap, keys.data_ptr(),
                                                     counts.data_ptr(), probs.data_ptr(), weights.data_ptr(), info.data_ptr(),
                                                     _stream_ptr(self.device))
         else:
-            st = self._lib.naqs_net_sample(self._h, int(n_samples), int(seed) & (2 ** 64 - 1), cap, keys.data_ptr(),
+            st = self._lib.naqs_net_sample(self._h, int(n_samples), _seed64(seed), cap, keys.data_ptr(),
                                            counts.data_ptr(), probs.data_ptr(), info.data_ptr(), _stream_ptr(self.device))
         _lib.check(st, "naqs_net_sample")
         m, overflow = info.tolist()
@@ -517,7 +548,7 @@ class FusedLogPsi:
         if self._samp is None:
             self._samp = torch.empty(2, dtype=torch.int64, device=dev)
         info_host = (ctypes.c_int64 * 2)(0, 0)
-        st = self._lib.naqs_vmc_sample_forward_eloc(self._h, ham._h, int(n_samples), int(seed) & (2 ** 64 - 1), cap, keys.data_ptr(),
+        st = self._lib.naqs_vmc_sample_forward_eloc(self._h, ham._h, int(n_samples), _seed64(seed), cap, keys.data_ptr(),
                                                     counts.data_ptr(), probs.data_ptr(), weights.data_ptr(), log_psi.data_ptr(),
                                                     eloc.data_ptr(), sums.data_ptr(), self._samp.data_ptr(), info_host,
                                                     _stream_ptr(dev))
@@ -543,48 +574,23 @@ class FusedLogPsi:
         keys = keys_out if keys_out is not None else torch.empty(cap, dtype=torch.int64, device=dev)
         if keys.dtype != torch.int64 or keys.numel() < cap or not keys.is_contiguous():
             raise ValueError("vmc_step: keys_out must be a contiguous int64 tensor of at least max_unique elements")
-        # the step's cap-sized outputs live in per-handle buffers (allocated once per cap: eight allocator calls per step were
-        # ~15 us of host time on a 0.2 ms step); they are valid until the next step of this handle — what the optimiser keeps
-        # across steps are the two device scalars (<E>, Var), which therefore get fresh storage every step
-        ob = getattr(self, "_onecall_bufs", None)
-        if ob is None or ob[0] != cap:
-            ob = self._onecall_bufs = (cap, torch.empty(cap, dtype=torch.int64, device=dev), torch.empty(cap, dtype=torch.float32, device=dev),
-                                       torch.empty(cap, dtype=torch.float64, device=dev), torch.empty((cap, 2), dtype=torch.float32, device=dev),
-                                       torch.empty((cap, 2), dtype=torch.float64, device=dev), torch.empty((cap, 2), dtype=torch.float32, device=dev))
-        _, counts, probs, weights, log_psi, eloc, g = ob
+        counts, probs, weights, log_psi, eloc, g = self._table_buffers(cap)
+        # what the optimiser keeps across steps are the two device scalars (<E>, Var), which therefore get fresh storage
+        # every step (the cap-sized outputs are only valid until the next step of this handle)
         small = torch.empty(6, dtype=torch.float64, device=dev)
         sums, ev = small[:4], small[4:]
-        if self._grad_flat is None:
-            self._grad_flat = torch.empty(self.n_params, dtype=torch.float32, device=dev)
-            self._grad_views, off = [], 0
-            for p in self.wf.param_list():
-                n = p.numel()
-                self._grad_views.append(self._grad_flat[off:off + n].view(p.shape))
-                off += n
         info = (ctypes.c_int64 * 3)(0, 0, 0)
-        if adam is not None:
-            grp = next(g_ for g_ in adam.param_groups if g_['params'])
-            flat, m1, m2, t = adam._flat, adam._m, adam._v, adam._t + 1
-            if flat.numel() != self.n_params:
-                raise ValueError("vmc_step: the optimiser's flat vector is not this network's")
-            hyper = (float(grp['lr']), float(grp['betas'][0]), float(grp['betas'][1]), float(grp['eps']), float(grp['weight_decay']))
-            ptrs = (flat.data_ptr(), m1.data_ptr(), m2.data_ptr())
-        else:
-            hyper, ptrs, t = (0.0, 0.0, 0.0, 0.0, 0.0), (None, None, None), 0
-        st = self._lib.naqs_vmc_step(self._h, ham._h, int(n_samples), int(seed) & (2 ** 64 - 1), cap, int(m_lo), int(m_hi),
+        ptrs, hyper, t = self._adam_args(adam, "vmc_step") if adam is not None else ((None, None, None), (0.0,) * 5, 0)
+        st = self._lib.naqs_vmc_step(self._h, ham._h, int(n_samples), _seed64(seed), cap, int(m_lo), int(m_hi),
                                      keys.data_ptr(), counts.data_ptr(), probs.data_ptr(), weights.data_ptr(), log_psi.data_ptr(),
-                                     eloc.data_ptr(), sums.data_ptr(), g.data_ptr(), ev.data_ptr(), self._grad_flat.data_ptr(),
-                                     ptrs[0], ptrs[1], ptrs[2], *hyper, t, info, _stream_ptr(dev))
+                                     eloc.data_ptr(), sums.data_ptr(), g.data_ptr(), ev.data_ptr(), self._ensure_grad_flat().data_ptr(),
+                                     *ptrs, *hyper, t, info, _stream_ptr(dev))
         _lib.check(st, "naqs_vmc_step")
         m, overflow, taken = int(info[0]), bool(info[1]), bool(info[2])
         if not taken:
             return False, m, overflow, None
         if adam is not None:
-            if not adam.state:
-                adam._bind_state()
-            adam._t = t
-            adam._opt_called = True          # (what torch's LR schedulers look at to see that a step preceded theirs)
-            self._flat = adam._flat
+            self._adam_stepped(adam, t)
         return True, m, False, (keys[:m], counts[:m], probs[:m], weights[:m], log_psi[:m], eloc[:m], sums, g[:m], ev)
 
     @torch.no_grad()
@@ -596,12 +602,7 @@ class FusedLogPsi:
         n_samples, sample_calls, ring_off, M [steps], ns [steps], t [steps], ev [steps, 2], sums [steps, 4], and the last step's
         table views keys / counts / probs / weights / log_psi / eloc / g)."""
         dev, cap = self.device, int(n_unq_max)
-        ob = getattr(self, "_onecall_bufs", None)
-        if ob is None or ob[0] != cap:
-            ob = self._onecall_bufs = (cap, torch.empty(cap, dtype=torch.int64, device=dev), torch.empty(cap, dtype=torch.float32, device=dev),
-                                       torch.empty(cap, dtype=torch.float64, device=dev), torch.empty((cap, 2), dtype=torch.float32, device=dev),
-                                       torch.empty((cap, 2), dtype=torch.float64, device=dev), torch.empty((cap, 2), dtype=torch.float32, device=dev))
-        _, counts, probs, weights, log_psi, eloc, g = ob
+        counts, probs, weights, log_psi, eloc, g = self._table_buffers(cap)
         if ring is None:
             kb = getattr(self, "_run_keys", None)
             if kb is None or kb.numel() < cap:
@@ -611,30 +612,21 @@ class FusedLogPsi:
             if ring.dtype != torch.int64 or not ring.is_contiguous() or ring.numel() < cap:
                 raise ValueError("vmc_run: the tracking buffer must be a contiguous int64 tensor of at least max_unique elements")
             keys_buf, ring_elems = ring, ring.numel()
-        if self._grad_flat is None:
-            self._grad_flat = torch.empty(self.n_params, dtype=torch.float32, device=dev)
-            self._grad_views, off = [], 0
-            for p in self.wf.param_list():
-                n = p.numel()
-                self._grad_views.append(self._grad_flat[off:off + n].view(p.shape))
-                off += n
         n = int(n_steps)
         ev = torch.empty((max(n, 1), 2), dtype=torch.float64, device=dev)
         sums = torch.empty((max(n, 1), 4), dtype=torch.float64, device=dev)
         m_log, ns_log, t_log = (ctypes.c_int64 * max(n, 1))(), (ctypes.c_int64 * max(n, 1))(), (ctypes.c_double * max(n, 1))()
         ev_cap = 64 + 4 * n
         events = (_lib.VmcEvent * ev_cap)()
-        grp = next(g_ for g_ in adam.param_groups if g_['params'])
-        if adam._flat.numel() != self.n_params:
-            raise ValueError("vmc_run: the optimiser's flat vector is not this network's")
+        ptrs, hyper, t_next = self._adam_args(adam, "vmc_run")
         a = _lib.VmcRunArgs()
         a.n_samples, a.n_samples_max = int(n_samples), int(n_samples_max)
         a.n_unq_samples_min, a.n_unq_samples_max = int(n_unq_min), cap
-        a.seed_base, a.sample_calls = int(seed_base) & (2 ** 64 - 1), int(sample_calls)
-        a.param_dev, a.exp_avg_dev, a.exp_avg_sq_dev = adam._flat.data_ptr(), adam._m.data_ptr(), adam._v.data_ptr()
-        a.grad_dev = self._grad_flat.data_ptr()
-        a.lr, a.beta1, a.beta2 = float(grp['lr']), float(grp['betas'][0]), float(grp['betas'][1])
-        a.eps, a.weight_decay, a.adam_step = float(grp['eps']), float(grp['weight_decay']), int(adam._t)
+        a.seed_base, a.sample_calls = _seed64(seed_base), int(sample_calls)
+        a.param_dev, a.exp_avg_dev, a.exp_avg_sq_dev = ptrs
+        a.grad_dev = self._ensure_grad_flat().data_ptr()
+        a.lr, a.beta1, a.beta2, a.eps, a.weight_decay = hyper
+        a.adam_step = int(t_next) - 1                      # (the steps done so far: the library counts on from here)
         a.keys_dev, a.ring_elems, a.ring_off = keys_buf.data_ptr(), int(ring_elems), int(ring_off)
         a.counts_dev, a.probs_dev, a.weights_dev = counts.data_ptr(), probs.data_ptr(), weights.data_ptr()
         a.logpsi_dev, a.eloc_dev, a.g_dev = log_psi.data_ptr(), eloc.data_ptr(), g.data_ptr()
@@ -652,11 +644,7 @@ class FusedLogPsi:
             error = exc
         done = int(a.steps_done)
         if done:
-            if not adam.state:
-                adam._bind_state()
-            adam._t = int(a.adam_step)
-            adam._opt_called = True
-            self._flat = adam._flat
+            self._adam_stepped(adam, int(a.adam_step))
         m_last = int(m_log[done - 1]) if done else 0
         k0 = int(a.last_keys_off)
         return dict(steps=done, stop_reason=int(a.stop_reason), error=error,
@@ -669,8 +657,8 @@ class FusedLogPsi:
     # ---- the row-sharded step (world > 1): four library calls, the three collectives between them (include/naqs_hip.h) ----
     def _step_buffers(self, cap, world, keys_out=None):
         """Per-handle buffers of the sharded step, allocated once per (cap, world): the step's outputs are views of them and
-        stay valid until the next step (the one-call step of a single process allocates per step; here the gather and
-        reduce buffers have to be persistent anyway)."""
+        stay valid until the next step, like ``_table_buffers``' of the single process's one-call step; the flat gradient
+        the step's backward writes and all-reduces is made here too."""
         key = (int(cap), int(world))
         sb = getattr(self, "_shard_bufs", None)
         if sb is None or sb["key"] != key:
@@ -684,13 +672,7 @@ class FusedLogPsi:
                 table=torch.empty((S_pad * int(world), 2), dtype=torch.float32, device=dev),
                 eloc=torch.empty((S_pad, 2), dtype=torch.float64, device=dev), g=torch.empty((S_pad, 2), dtype=torch.float32, device=dev),
                 ext=torch.empty(8, dtype=torch.float64, device=dev), ev=torch.empty(2, dtype=torch.float64, device=dev))
-        if self._grad_flat is None:
-            self._grad_flat = torch.empty(self.n_params, dtype=torch.float32, device=self.device)
-            self._grad_views, off = [], 0
-            for p in self.wf.param_list():
-                n = p.numel()
-                self._grad_views.append(self._grad_flat[off:off + n].view(p.shape))
-                off += n
+        self._ensure_grad_flat()
         return sb
 
     @torch.no_grad()
@@ -704,7 +686,7 @@ class FusedLogPsi:
         if keys.dtype != torch.int64 or keys.numel() < cap or not keys.is_contiguous():
             raise ValueError("shard_sample_forward: keys_out must be a contiguous int64 tensor of at least max_unique elements")
         info = (ctypes.c_int64 * 3)(0, 0, 0)
-        st = self._lib.naqs_vmc_shard_sample_forward(self._h, int(n_samples), int(seed) & (2 ** 64 - 1), cap, int(m_lo), int(m_hi),
+        st = self._lib.naqs_vmc_shard_sample_forward(self._h, int(n_samples), _seed64(seed), cap, int(m_lo), int(m_hi),
                                                      int(rank), int(world), keys.data_ptr(), sb["counts"].data_ptr(),
                                                      sb["probs"].data_ptr(), sb["weights"].data_ptr(), sb["mine"].data_ptr(), info,
                                                      _stream_ptr(self.device))
@@ -737,17 +719,10 @@ class FusedLogPsi:
     @torch.no_grad()
     def shard_update(self, adam):
         """Call 4 (``naqs_vmc_shard_update``): Adam on the flat parameter vector with the all-reduced gradient + re-pack."""
-        grp = next(g_ for g_ in adam.param_groups if g_['params'])
-        t = adam._t + 1
-        st = self._lib.naqs_vmc_shard_update(self._h, self._grad_flat.data_ptr(), adam._flat.data_ptr(), adam._m.data_ptr(),
-                                             adam._v.data_ptr(), float(grp['lr']), float(grp['betas'][0]), float(grp['betas'][1]),
-                                             float(grp['eps']), float(grp['weight_decay']), t, _stream_ptr(self.device))
+        ptrs, hyper, t = self._adam_args(adam, "shard_update")
+        st = self._lib.naqs_vmc_shard_update(self._h, self._grad_flat.data_ptr(), *ptrs, *hyper, t, _stream_ptr(self.device))
         _lib.check(st, "naqs_vmc_shard_update")
-        if not adam.state:
-            adam._bind_state()
-        adam._t = t
-        adam._opt_called = True
-        self._flat = adam._flat
+        self._adam_stepped(adam, t)
 
     def prof_enable(self, n, stride=1):
         _lib.check(self._lib.naqs_net_prof_enable(self._h, int(n)), "naqs_net_prof_enable")

@@ -80,6 +80,29 @@ def vmc_loss(log_psi, e_loc, weights, e_mean):
     return 2.0 * (weights * (log_psi[:, 0] * ec[:, 0] - log_psi[:, 1] * ec[:, 1])).sum()
 
 
+def same_on_all_ranks(pairs, world):
+    """The same-table proof on ``pairs``, the all-reduced float64 vector of what each of ``world`` ranks contributed as
+    (x, x^2, y, y^2, ...): world * sum x^2 == (sum x)^2 iff all ranks contributed the same x (Cauchy-Schwarz; exact while
+    these integers stay below 2^53).  -> bool scalar on the vector's device: every pair agrees."""
+    return (world * pairs[1::2] == pairs[0::2] * pairs[0::2]).all()
+
+
+def nan_unless(ok, ev):
+    """``ev``, or NaN where the proof failed: ranks that sampled different tables must not report a plausible energy."""
+    return torch.where(ok, ev, torch.full_like(ev, float("nan")))
+
+
+class _StepForward:
+    """What the forward stage of ``_SGD_step`` hands to the later ones: log psi of this rank's rows and of the whole table,
+    and — graph-free forms — the fused handle, the backward token, the single-GPU call's (log psi, token, E_loc, sums) and
+    the exact step's (keys, log psi) buffers."""
+    lp_all = fused = saved = pre = exact_bufs = None
+
+    def __init__(self, lp_mine, **later):
+        self.lp_mine = lp_mine
+        self.__dict__.update(later)
+
+
 _GC_FROZEN = False
 
 
@@ -328,9 +351,13 @@ class OptimizerBase:
         p = (flat.detach().view(torch.int32).sum(dtype=torch.int64) & 0xFFFFF).double()
         ext = torch.stack([m, m * m, c, c * c, p, p * p])
         dist.all_reduce(ext)
-        bad = ~((world * ext[1] == ext[0] * ext[0]) & (world * ext[3] == ext[2] * ext[2]) & (world * ext[5] == ext[4] * ext[4]))
-        self._shard_mismatch = bad if self._shard_mismatch is None else self._shard_mismatch | bad
+        self._record_agreement(same_on_all_ranks(ext, world))
         self._proof_at = (self.n_steps, ext)
+
+    def _record_agreement(self, ok):
+        """OR a failed same-table proof into ``_shard_mismatch`` (read at the next log flush: ``_check_shards``).  -> ok"""
+        self._shard_mismatch = ~ok if self._shard_mismatch is None else self._shard_mismatch | ~ok
+        return ok
 
     def reset_log(self):
         self._pending_log = []
@@ -647,171 +674,194 @@ class OptimizerBase:
         M = keys.shape[0]
         if self.track_sampled_idxs:          # energy.py:300; folded into the Counter in batches (no per-step sync)
             self._track_sampled(keys)
-        # shard of rows this rank owns (the whole table when single-process)
-        b, e_ = shard_bounds(M, rank, world)
-        saved = None
-        exact, exact_bufs = self.exact_local_energies, None
-        if exact and dist is not None:           # (unreachable through _choose_dist_mode: exact mode never shards)
+        b, e_ = shard_bounds(M, rank, world)           # the rows this rank owns (the whole table when single-process)
+        if self.exact_local_energies and dist is not None:   # (unreachable through _choose_dist_mode: exact mode never shards)
             raise NotImplementedError("exact local energies in a row-sharded step")
         if log_psi is not None:
             # reference-style call: log psi of the whole table, carrying gradients
-            lp_all, lp_mine = log_psi.reshape(-1, 2), log_psi.reshape(-1, 2)[b:e_]
+            fw = _StepForward(log_psi.reshape(-1, 2)[b:e_], lp_all=log_psi.reshape(-1, 2))
         else:
             # gradients only for the owned rows; the table needed for the psi look-ups is evaluated
             # without autograd (the rows of other ranks are theirs to differentiate)
-            fused = self.wavefunction.fused(need_phase=True) if self.use_fused else None
-            pre = None
-            quirk = self._eloc_keys(keys) is not keys
-            if (exact and fused is not None and regularisation_loss is None and not self.normalize_grads
-                    and fused.train_mode == "hip" and sample_weights is not None):
-                # exact local energies: the table's keys and log psi go to the front of the buffers that the library call
-                # below appends the connected states to
-                exact_bufs = self._exact_buffers(M)
-                exact_bufs[0][:M].copy_(keys)
-                lp_mine, saved = fused.forward_saved(exact_bufs[0][:M], out=exact_bufs[1][:M])
-            elif (fused is not None and regularisation_loss is None and not self.normalize_grads and world == 1 and not exact
-                    and fused.train_mode == "hip" and sample_weights is not None and not quirk
-                    and os.environ.get("NAQS_TRAIN_FUSED_ELOC", "1") == "1"):
-                # single GPU: forward (activations kept) + E_loc + weighted sums in one library call — or already done by
-                # the sampler's call for exactly these keys and weights (get_samples, training loop)
-                pf = getattr(self, "_prefused", None)
-                self._prefused = None
-                if pf is not None and pf[0] is states_idx and sample_weights is self._sample_weights:
-                    pre = pf[1]
-                else:
-                    pre = fused.forward_saved_with_local_energy(self.pauli_hamiltonian, keys, sample_weights.reshape(-1))
-                lp_mine, saved = pre[0], pre[1]
-            elif fused is not None and regularisation_loss is None and not self.normalize_grads:
-                # HIP amplitude forward/backward + explicit chain rule of the phase MLP: no autograd graph at all
-                lp_mine, saved = fused.forward_saved(keys[b:e_])
-            elif fused is not None and not fused.aggregate and not fused.comb:     # same kernels behind a torch.autograd.Function
-                lp_mine = fused.log_psi_train(keys[b:e_])
+            fw = self._step_forward(states, states_idx, keys, sample_weights, regularisation_loss, b, e_, world)
+            fw.lp_all = fw.lp_mine if world == 1 else self._gather_table(dist, fw.lp_mine, M, b, e_, world)
+        w = self._step_weights(sample_weights, fw.lp_all)
+        e_loc, sums = self._step_local_energy(fw, keys, w, b, e_)
+        shard_ok = None
+        if dist:
+            sums, shard_ok = self._shard_proof(dist, keys, sums, world)
+        self.optimizer.zero_grad()
+        ev = self._step_update(fw, e_loc, w, sums, b, e_, world, regularisation_loss)
+        if dist:
+            self._all_reduce_grads(dist, fw)
+        self._step_optimizer(fw)
+        with torch.no_grad():                                           # energy.py:367-377
+            if ev is None:
+                energy = sums[0] / sums[3]
+                ev = torch.stack([energy, sums[2] / sums[3] - energy * energy])
+            if shard_ok is not None:
+                ev = nan_unless(shard_ok, ev)
+        if lazy:        # device scalars: the caller reads them later, so the host can queue the next step meanwhile
+            return ev
+        self._check_shards()
+        energy, variance = ev.tolist()
+        return float(energy), float(variance)
+
+    def _step_forward(self, states, states_idx, keys, sample_weights, regularisation_loss, b, e_, world):
+        """Stage 1 of ``_SGD_step``: log psi of rows [b, e_) in the cheapest of five forms.  The single-GPU fused form is what
+        ``_can_prefuse`` announces to the sampler, but not the same predicate: here the caller's ``sample_weights``, the
+        table at hand (``quirk``) and ``world`` decide too, NAQS_TRAIN_PREFUSE does not, and the natural gradient takes it."""
+        fused = self.wavefunction.fused(need_phase=True) if self.use_fused else None
+        quirk = self._eloc_keys(keys) is not keys
+        graph_free = fused is not None and regularisation_loss is None and not self.normalize_grads
+        hip_weighted = graph_free and fused.train_mode == "hip" and sample_weights is not None
+        if self.exact_local_energies and hip_weighted:
+            # exact local energies: the table's keys and log psi go to the front of the buffers that the library call
+            # of the next stage appends the connected states to
+            M = keys.shape[0]
+            bufs = self._exact_buffers(M)
+            bufs[0][:M].copy_(keys)
+            lp, saved = fused.forward_saved(bufs[0][:M], out=bufs[1][:M])
+            return _StepForward(lp, fused=fused, saved=saved, exact_bufs=bufs)
+        if hip_weighted and world == 1 and not quirk and os.environ.get("NAQS_TRAIN_FUSED_ELOC", "1") == "1":
+            # single GPU: forward (activations kept) + E_loc + weighted sums in one library call — or already done by
+            # the sampler's call for exactly these keys and weights (get_samples, training loop)
+            pf = getattr(self, "_prefused", None)
+            self._prefused = None
+            if pf is not None and pf[0] is states_idx and sample_weights is self._sample_weights:
+                pre = pf[1]
             else:
-                lp_mine = self.wavefunction.log_psi(states[b:e_]).reshape(-1, 2)
-            if world == 1:
-                lp_all = lp_mine
-            else:
-                # the table every rank's E_loc rows look psi_j up in: ONE all-gather of the ranks' own (log|psi|, phase)
-                # shards — no rank evaluates the network on rows it does not own (what `bench.py --shard rows`
-                # measures).  The contribution has a size every rank computes WITHOUT looking at its table (rows for the
-                # largest table the sampler may return, n_unq_samples_max): ranks whose samplers diverged then still meet in
-                # a well-formed collective and the key-checksum proof below reports them, instead of a size mismatch
-                # wedging the communicator.  The bytes are cheap (100 KB per rank at the published settings; latency-bound).
-                S = -(-M // world)
-                S_pad = max(S, -(-int(self.n_unq_samples_max) // world)) if getattr(self, "n_unq_samples_max", None) else S
-                gb = getattr(self, "_gather_bufs", None)
-                if gb is None or gb[0].shape[0] != S_pad or gb[1].shape[0] != S_pad * world:
-                    gb = self._gather_bufs = (torch.zeros((S_pad, 2), dtype=torch.float32, device=self.device),
-                                             torch.empty((S_pad * world, 2), dtype=torch.float32, device=self.device))
-                mine, table = gb                       # rows past my shard keep old values: they are never looked at (>= M)
-                mine[:e_ - b] = lp_mine.detach()
-                dist.all_gather_into_tensor(table, mine)
-                lp_all = table.view(world, S_pad, 2)[:, :S].reshape(-1, 2)[:M]
+                pre = fused.forward_saved_with_local_energy(self.pauli_hamiltonian, keys, sample_weights.reshape(-1))
+            return _StepForward(pre[0], fused=fused, saved=pre[1], pre=pre)
+        if graph_free:
+            # HIP amplitude forward/backward + explicit chain rule of the phase MLP: no autograd graph at all
+            lp, saved = fused.forward_saved(keys[b:e_])
+            return _StepForward(lp, fused=fused, saved=saved)
+        if fused is not None and not fused.aggregate and not fused.comb:     # same kernels behind a torch.autograd.Function
+            return _StepForward(fused.log_psi_train(keys[b:e_]), fused=fused)
+        return _StepForward(self.wavefunction.log_psi(states[b:e_]).reshape(-1, 2), fused=fused)
+
+    def _gather_table(self, dist, lp_mine, M, b, e_, world):
+        """Stage 2 (sharded): the table every rank's E_loc rows look psi_j up in: ONE all-gather of the ranks' own (log|psi|,
+        phase) shards — no rank evaluates the network on rows it does not own (what `bench.py --shard rows`
+        measures).  The contribution has a size every rank computes WITHOUT looking at its table (rows for the largest table
+        the sampler may return, n_unq_samples_max): ranks whose samplers diverged then still meet in a well-formed collective
+        and the key-checksum proof reports them, instead of a size mismatch wedging the communicator (100 KB per rank)."""
+        S = -(-M // world)
+        S_pad = max(S, -(-int(self.n_unq_samples_max) // world)) if getattr(self, "n_unq_samples_max", None) else S
+        gb = getattr(self, "_gather_bufs", None)
+        if gb is None or gb[0].shape[0] != S_pad or gb[1].shape[0] != S_pad * world:
+            gb = self._gather_bufs = (torch.zeros((S_pad, 2), dtype=torch.float32, device=self.device),
+                                     torch.empty((S_pad * world, 2), dtype=torch.float32, device=self.device))
+        mine, table = gb                       # rows past my shard keep old values: they are never looked at (>= M)
+        mine[:e_ - b] = lp_mine.detach()
+        dist.all_gather_into_tensor(table, mine)
+        return table.view(world, S_pad, 2)[:, :S].reshape(-1, 2)[:M]
+
+    def _step_weights(self, sample_weights, lp_all):
+        """The table's weights as float64 [M]: the caller's, or |psi|^2 (``reweight_samples_by_psi``)."""
         if sample_weights is None:
             if not self.reweight_samples_by_psi:
                 raise NotImplementedError("Re-weighting by the number of samples is not yet implemented.")
             sample_weights = lp_all.detach()[..., 0].exp().pow(2)
             if self.normalise_psi:
                 sample_weights = sample_weights / sample_weights.sum()
-        w = sample_weights.reshape(-1).to(self.device, torch.float64)
+        return sample_weights.reshape(-1).to(self.device, torch.float64)
 
-        # E_loc of the owned rows + (sum w Re, sum w Im, sum w Re^2, sum w) in one launch
-        if log_psi is None and pre is not None:
-            e_loc, sums = pre[2], pre[3]
-        elif exact:
-            # psi on every connected state: the library call on the optimiser's buffers, or — networks on the announced
-            # fallback, the BLAS phase mode, a caller's own log psi — the evaluation path's Python evaluator
-            if exact_bufs is not None:
-                e_loc, sums, n_conn = self._exact_train_local_energy(fused, exact_bufs[0], exact_bufs[1], M, w)
-            else:
-                e_loc, sums, n_conn = self._exact_local_energy(keys, log_psi=lp_all.detach(), max_table=self.exact_max_table,
-                                                               weights=w)
-            self._n_connected_pending += n_conn
+    def _step_local_energy(self, fw, keys, w, b, e_):
+        """Stage 3: E_loc of the owned rows + (sum w Re, sum w Im, sum w Re^2, sum w) in one launch — already there when the
+        forward stage took the single-GPU call."""
+        if fw.pre is not None:
+            return fw.pre[2], fw.pre[3]
+        if not self.exact_local_energies:
+            return self.pauli_hamiltonian.local_energy(self._eloc_keys(keys), fw.lp_all.detach(), kind="log_psi", row_begin=b,
+                                                       n_rows=e_ - b, weights=w[b:e_])
+        # psi on every connected state: the library call on the optimiser's buffers, or — networks on the announced
+        # fallback, the BLAS phase mode, a caller's own log psi — the evaluation path's Python evaluator
+        if fw.exact_bufs is not None:
+            e_loc, sums, n_conn = self._exact_train_local_energy(fw.fused, fw.exact_bufs[0], fw.exact_bufs[1], keys.shape[0], w)
         else:
-            e_loc, sums = self.pauli_hamiltonian.local_energy(self._eloc_keys(keys), lp_all.detach(), kind="log_psi", row_begin=b,
-                                                              n_rows=e_ - b, weights=w[b:e_])
-        shard_ok = None
-        if dist:
-            # one collective for the accumulators AND a proof that every rank sharded the same table: with
-            # (M, M^2, c, c^2) appended (c = 20 low bits of the key sum), W * sum x^2 == (sum x)^2 holds iff all
-            # ranks contributed the same x (Cauchy-Schwarz; everything is an exact integer in float64)
-            if self.device.type == "cuda":
-                # (one launch of the library instead of eight tiny torch kernels and a host-to-device copy of M: at
-                # M ~ 10^3 the sharded step is bound by its launches)
-                from . import _lib
-                from .fused import _stream_ptr
-                ext = torch.empty(8, dtype=torch.float64, device=self.device)
-                _lib.check(_lib.load_library().naqs_shard_proof(M, keys.data_ptr(), sums.data_ptr(), ext.data_ptr(),
-                                                                 _stream_ptr(self.device)), "naqs_shard_proof")
-            else:
-                c = (keys.sum() & 0xFFFFF).double()
-                m = torch.tensor(float(M), dtype=torch.float64, device=self.device)
-                ext = torch.cat([sums, torch.stack([m, m * m, c, c * c])])
-            dist.all_reduce(ext)
-            sums = ext[:4]
-            shard_ok = (world * ext[5] == ext[4] * ext[4]) & (world * ext[7] == ext[6] * ext[6])
-            self._shard_mismatch = (~shard_ok if self._shard_mismatch is None else self._shard_mismatch | ~shard_ok)
-        self.optimizer.zero_grad()
-        ev = None
-        natural = getattr(self, "natural_gradient", None)
+            e_loc, sums, n_conn = self._exact_local_energy(keys, log_psi=fw.lp_all.detach(), max_table=self.exact_max_table,
+                                                           weights=w)
+        self._n_connected_pending += n_conn
+        return e_loc, sums
+
+    def _shard_proof(self, dist, keys, sums, world):
+        """Stage 4 (sharded): one collective for the accumulators AND the proof that every rank sharded the same table: (M, M^2,
+        c, c^2) behind the sums, c = 20 low bits of the key sum (``same_on_all_ranks``).  -> (all-reduced sums [4], agreement)"""
+        M = keys.shape[0]
+        if self.device.type == "cuda":
+            # (one launch of the library instead of eight tiny torch kernels and a host-to-device copy of M: at
+            # M ~ 10^3 the sharded step is bound by its launches)
+            from . import _lib
+            from .fused import _stream_ptr
+            ext = torch.empty(8, dtype=torch.float64, device=self.device)
+            _lib.check(_lib.load_library().naqs_shard_proof(M, keys.data_ptr(), sums.data_ptr(), ext.data_ptr(),
+                                                             _stream_ptr(self.device)), "naqs_shard_proof")
+        else:
+            c = (keys.sum() & 0xFFFFF).double()
+            m = torch.tensor(float(M), dtype=torch.float64, device=self.device)
+            ext = torch.cat([sums, torch.stack([m, m * m, c, c * c])])
+        dist.all_reduce(ext)
+        return ext[:4], self._record_agreement(same_on_all_ranks(ext[4:], world))
+
+    def _step_update(self, fw, e_loc, w, sums, b, e_, world, regularisation_loss):
+        """Stage 5: the parameters' gradients (or, natural gradient, the update itself) in one of three forms.
+        -> (<E>, Var) where the form's launch leaves it on the device, else None"""
+        natural, saved = getattr(self, "natural_gradient", None), fw.saved
         if natural and (saved is None or saved[1] is not None or world != 1):
             raise NotImplementedError("natural gradient: the step needs the HIP training forward of the whole table (a fused network in "
                                       "HIP mode, sampled weights, no regularisation loss, no normalize_grads, no caller's log psi)")
         if natural:
             # minSR: the loss seeds as below, the two M x M systems from the Gram kernels, two float64 Cholesky solves on the
             # device, the direction as a backward pass with the solutions as seeds, and theta -= lr * direction (no Adam)
-            g, ev = fused.vmc_loss_grad(e_loc, w.contiguous(), sums, with_energy=True)
-            self._natural_gradient_update(fused, saved, w.contiguous(), g)
-            self._loss_terms, self._last_loss = (g, lp_mine), None
+            g, ev = fw.fused.vmc_loss_grad(e_loc, w.contiguous(), sums, with_energy=True)
+            self._natural_gradient_update(fw.fused, saved, w.contiguous(), g)
         elif saved is not None:
             # d loss / d log psi of vmc_loss, written out: (2 w Re(E_loc - <E>), -2 w Im(E_loc - <E>)); the same launch
             # leaves (<E>, Var) of energy.py:372-375 on the device
-            g, ev = fused.backward_from_local_energy(saved, e_loc, w[b:e_].contiguous(), sums)
-            self._loss_terms, self._last_loss = (g, lp_mine), None
+            g, ev = fw.fused.backward_from_local_energy(saved, e_loc, w[b:e_].contiguous(), sums)
         else:
             e_mean = torch.stack([sums[0], sums[1]])                    # (sum w E_loc), like energy.py:328 (w not renormalised)
-            loss = vmc_loss(lp_mine, e_loc.to(lp_mine.dtype), w[b:e_].to(lp_mine.dtype), e_mean.to(lp_mine.dtype))
+            lp = fw.lp_mine
+            loss = vmc_loss(lp, e_loc.to(lp.dtype), w[b:e_].to(lp.dtype), e_mean.to(lp.dtype))
             if self.normalize_grads:
                 loss = loss / loss.detach().abs()
             if regularisation_loss is not None:
                 loss = loss + regularisation_loss
             loss.backward()
             self._loss_terms, self._last_loss = None, loss.detach()
-        if dist:
-            params = [p for g in self.optimizer.param_groups for p in g['params'] if p.grad is not None]
-            gflat = getattr(fused, "_grad_flat", None) if saved is not None else None
-            if gflat is not None and params and params[0].grad.data_ptr() == gflat.data_ptr():
-                dist.all_reduce(gflat)                                  # the gradients ARE one flat buffer: in place
-            else:
-                flat = torch.cat([p.grad.reshape(-1) for p in params])
-                dist.all_reduce(flat)                                   # shards SUM to the full-batch gradient
-                off = 0
-                for p in params:
-                    p.grad.copy_(flat[off:off + p.numel()].view_as(p))
-                    off += p.numel()
-        if not natural:
+            return None
+        self._loss_terms, self._last_loss = (g, fw.lp_mine), None
+        return ev
+
+    def _all_reduce_grads(self, dist, fw):
+        """Stage 6 (sharded): the shards' gradients SUM to the full-batch gradient."""
+        params = [p for g in self.optimizer.param_groups for p in g['params'] if p.grad is not None]
+        gflat = getattr(fw.fused, "_grad_flat", None) if fw.saved is not None else None
+        if gflat is not None and params and params[0].grad.data_ptr() == gflat.data_ptr():
+            dist.all_reduce(gflat)                                  # the gradients ARE one flat buffer: in place
+        else:
+            flat = torch.cat([p.grad.reshape(-1) for p in params])
+            dist.all_reduce(flat)
+            off = 0
+            for p in params:
+                p.grad.copy_(flat[off:off + p.numel()].view_as(p))
+                off += p.numel()
+
+    def _step_optimizer(self, fw):
+        """Stage 7: the optimiser's step (the natural gradient has applied its own), the early re-pack, the scheduler."""
+        if not getattr(self, "natural_gradient", None):
             self._clip_grads()
             self.optimizer.step()
         self.wavefunction.parameters_changed()
-        if self.use_fused and saved is not None and os.environ.get("NAQS_TRAIN_EARLY_REFRESH", "1") == "1":
+        if self.use_fused and fw.saved is not None and os.environ.get("NAQS_TRAIN_EARLY_REFRESH", "1") == "1":
             # re-pack the kernels' weight layouts NOW, behind the optimiser launch, instead of at the start of the next
             # sampling call: the host gets there tens of microseconds later and the GPU would wait for it
             self.wavefunction.fused(need_phase=True)
         self.optimizer.zero_grad()
         if self.scheduler is not None:
             self.scheduler.step()
-
-        with torch.no_grad():                                           # energy.py:367-377
-            if ev is None:
-                energy = sums[0] / sums[3]
-                ev = torch.stack([energy, sums[2] / sums[3] - energy * energy])
-            if shard_ok is not None:        # ranks that sampled different tables must not report a plausible energy
-                ev = torch.where(shard_ok, ev, torch.full_like(ev, float("nan")))
-        if lazy:        # device scalars: the caller reads them later, so the host can queue the next step meanwhile
-            return ev
-        self._check_shards()
-        energy, variance = ev.tolist()
-        return float(energy), float(variance)
 
     def _natural_gradient_update(self, fused, saved, w, g):
         """theta -= lr * [X_a^T (T_a + lambda I)^-1 y_a + X_phi^T (T_phi + lambda I)^-1 y_phi] (``FusedLogPsi.sr_gram`` /
@@ -1042,49 +1092,67 @@ class PartialSamplingOptimizer(OptimizerBase):
         return self._can_prefuse() and self._onecall_update_conditions()
 
     def _onecall_step(self):
-        """get_samples (adaptive sample count, energy.py:936-971) + _SGD_step (energy.py:273-377) through
-        ``FusedLogPsi.vmc_step``: the library abandons a step right after sampling when get_samples would have re-sampled
-        (tree overflow, or too few unique samples while the count may still grow), and this loop then adapts n_samples with
-        the reference's rules and messages.  -> (counts, weights, ev) of the step that was taken."""
-        wf = self.wavefunction
-        fused = wf.fused(need_phase=True)
+        """get_samples + _SGD_step (energy.py:936-971, 273-377) through ``FusedLogPsi.vmc_step``: the library abandons a step
+        right after sampling when get_samples would have re-sampled (tree overflow, or too few unique samples while the count
+        may still grow) and ``_resample_until_taken`` adapts n_samples.  -> (counts, weights, ev) of the step that was taken."""
+        fused = self.wavefunction.fused(need_phase=True)
+        keys, counts, probs, weights, lp, e_loc, sums, g, ev = self._resample_until_taken(
+            lambda m_lo, seed, slot: fused.vmc_step(self.pauli_hamiltonian, self.n_samples, seed, self.n_unq_samples_max, m_lo,
+                                                    self.n_unq_samples_max, adam=self.optimizer, keys_out=slot))
+        self._book_step(keys, weights, g, lp, int(keys.shape[0]), scheduler=True)
+        return counts, weights, ev
+
+    def _n_samples_free(self):
+        """Whether the sample count may still move: it sits on neither of its bounds (energy.py:953)."""
+        return (self.n_samples != self.n_unq_samples_min) and (self.n_samples != self.n_samples_max)
+
+    @staticmethod
+    def _adapt_message(n_unq, action, n_samples, epoch):
+        """The reference's line for a sample count that grew (action > 0) or shrank to ``n_samples`` (energy.py:958-969)."""
+        what = "increasing batch size" if action > 0 else "decreasing batch size"
+        return f"\t...{n_unq} unique samples generated --> {what} to {n_samples / 1e6:.1f}M at epoch {epoch}."
+
+    def _adapt_n_samples(self, n_unq, completed, last_action):
+        """The reference's adaptive sample count (energy.py:936-971), the only place that moves ``n_samples``: x10 after too few
+        unique samples, /10 after too many or a tree overflow (``completed`` False); never against ``last_action`` (no
+        oscillation), and off a bound only after an overflow.  -> +1 grew, -1 shrank or overflowed (draw again), 0 keep."""
+        n_unq, action = (n_unq, 0) if completed else (self.n_unq_samples_max + 1, -1)
+        grow = n_unq < self.n_unq_samples_min and last_action >= 0
+        if (self._n_samples_free() or not completed) and (grow or (n_unq > self.n_unq_samples_max and last_action <= 0)):
+            action = 1 if grow else -1
+            self.n_samples = int(min(self.n_samples * 10, self.n_samples_max) if grow
+                                 else max(self.n_samples / 10, self.n_unq_samples_min))
+            print(self._adapt_message(n_unq, action, self.n_samples, self.n_epochs))
+        return action
+
+    def _resample_until_taken(self, attempt):
+        """The loop of the step forms whose library call abandons a step right after sampling.  Per attempt: ONE sampler seed,
+        then the tracking buffer's slot, then ``attempt(m_lo, seed, slot) -> (taken, n_unq, overflow, payload)`` (m_lo: abandon
+        below this unique count; 0 when the count may not grow); if abandoned, ``_adapt_n_samples``.  -> the taken payload."""
         last_action = 0
         while True:
-            free = (self.n_samples != self.n_unq_samples_min) and (self.n_samples != self.n_samples_max)
-            m_lo = self.n_unq_samples_min if (free and last_action >= 0) else 0
-            seed = wf._next_sample_seed(self.generator)
+            m_lo = self.n_unq_samples_min if (self._n_samples_free() and last_action >= 0) else 0
+            seed = self.wavefunction._next_sample_seed(self.generator)
             slot = self._sampled_ring_slot(int(self.n_unq_samples_max)) if self.track_sampled_idxs else None
-            taken, n_unq, overflow, out = fused.vmc_step(self.pauli_hamiltonian, self.n_samples, seed, self.n_unq_samples_max,
-                                                          m_lo, self.n_unq_samples_max, adam=self.optimizer, keys_out=slot)
+            taken, n_unq, overflow, payload = attempt(m_lo, seed, slot)
             if taken:
-                break
-            action = 0
+                return payload
             if overflow:
                 print("MaxBatchSizeExceededError")
-                n_unq, action = self.n_unq_samples_max + 1, -1
-            if free or overflow:
-                if n_unq < self.n_unq_samples_min and last_action >= 0:
-                    action = 1
-                    self.n_samples = int(min(self.n_samples * 10, self.n_samples_max))
-                    print(f"\t...{n_unq} unique samples generated --> increasing batch size to "
-                          f"{self.n_samples / 1e6:.1f}M at epoch {self.n_epochs}.")
-                elif n_unq > self.n_unq_samples_max and last_action <= 0:
-                    action = -1
-                    self.n_samples = int(max(self.n_samples / 10, self.n_unq_samples_min))
-                    print(f"\t...{n_unq} unique samples generated --> decreasing batch size to "
-                          f"{self.n_samples / 1e6:.1f}M at epoch {self.n_epochs}.")
-            if action == 0:
+            last_action = self._adapt_n_samples(n_unq, not overflow, last_action)
+            if last_action == 0:
                 raise RuntimeError(f"VMC step abandoned without a reason to re-sample (M={n_unq})")
-            last_action = action
-        keys, counts, probs, weights, lp, e_loc, sums, g, ev = out
-        wf.fused_repacked()
+
+    def _book_step(self, keys, weights, g, lp, n_tracked, scheduler):
+        """After a step taken inside the library: the weights are re-packed, the table and the loss terms are the step's,
+        ``n_tracked`` more keys are in the tracking buffer already (energy.py:300); ``scheduler``: the form has one to step."""
+        self.wavefunction.fused_repacked()
         self._sample_keys, self._sample_weights, self._prefused = keys, weights, None
         if self.track_sampled_idxs:
-            self._sampled_ring_off += int(keys.shape[0])       # the keys are in the tracking buffer already (energy.py:300)
+            self._sampled_ring_off += n_tracked
         self._loss_terms, self._last_loss = (g, lp), None
-        if self.scheduler is not None:
+        if scheduler and self.scheduler is not None:
             self.scheduler.step()
-        return counts, weights, ev
 
     def _can_shard_onecall(self):
         """The sharded step as four library calls (``FusedLogPsi.shard_*``): the one-call step's conditions (one shared
@@ -1096,87 +1164,60 @@ class PartialSamplingOptimizer(OptimizerBase):
     def _sharded_onecall_step(self):
         """One row-sharded VMC step = four library calls and three collectives (include/naqs_hip.h): sampler +
         forward of my rows | all-gather | E_loc of my rows + sums + proof | all-reduce | backward | all-reduce | Adam + re-pack.
-        The adaptive sample count is ``_onecall_step``'s.  -> (counts, weights, ev)."""
+        The adaptive sample count is ``_resample_until_taken``'s.  -> (counts, weights, ev)."""
         dist = self._active_dist()
         world, rank = dist.get_world_size(), dist.get_rank()
-        wf = self.wavefunction
-        fused = wf.fused(need_phase=True)
-        last_action = 0
-        while True:
-            free = (self.n_samples != self.n_unq_samples_min) and (self.n_samples != self.n_samples_max)
-            m_lo = self.n_unq_samples_min if (free and last_action >= 0) else 0
-            seed = wf._next_sample_seed(self.generator)
-            slot = self._sampled_ring_slot(int(self.n_unq_samples_max)) if self.track_sampled_idxs else None
-            taken, n_unq, overflow, sb = fused.shard_sample_forward(self.n_samples, seed, self.n_unq_samples_max, m_lo,
-                                                                    self.n_unq_samples_max, rank, world, keys_out=slot)
-            if taken:
-                break
-            action = 0
-            if overflow:
-                print("MaxBatchSizeExceededError")
-                n_unq, action = self.n_unq_samples_max + 1, -1
-            if free or overflow:
-                if n_unq < self.n_unq_samples_min and last_action >= 0:
-                    action = 1
-                    self.n_samples = int(min(self.n_samples * 10, self.n_samples_max))
-                    print(f"\t...{n_unq} unique samples generated --> increasing batch size to "
-                          f"{self.n_samples / 1e6:.1f}M at epoch {self.n_epochs}.")
-                elif n_unq > self.n_unq_samples_max and last_action <= 0:
-                    action = -1
-                    self.n_samples = int(max(self.n_samples / 10, self.n_unq_samples_min))
-                    print(f"\t...{n_unq} unique samples generated --> decreasing batch size to "
-                          f"{self.n_samples / 1e6:.1f}M at epoch {self.n_epochs}.")
-            if action == 0:
-                raise RuntimeError(f"VMC step abandoned without a reason to re-sample (M={n_unq})")
-            last_action = action
-        M = n_unq
-        prof = os.environ.get("NAQS_SHARD_PROFILE") == "1"             # developer aid: synchronised per-stage wall times
-        if prof:
-            torch.cuda.synchronize(); t_ = [time.perf_counter()]
-            def mark():
-                torch.cuda.synchronize(); t_.append(time.perf_counter())
-        else:
-            def mark():
-                pass
+        fused = self.wavefunction.fused(need_phase=True)
+
+        def attempt(m_lo, seed, slot):
+            taken, M, overflow, sb = fused.shard_sample_forward(self.n_samples, seed, self.n_unq_samples_max, m_lo,
+                                                                self.n_unq_samples_max, rank, world, keys_out=slot)
+            return taken, M, overflow, (M, sb)
+        M, sb = self._resample_until_taken(attempt)
+        mark, report = self._shard_stage_timer()
         dist.all_gather_into_tensor(sb["table"], sb["mine"])           # equal padded shards: [world][S_pad][2]
         mark()
         b, e = fused.shard_eloc(self.pauli_hamiltonian, sb, M, rank, world)
         mark()
-        ext = sb["ext"]
-        dist.all_reduce(ext)
-        shard_ok = (world * ext[5] == ext[4] * ext[4]) & (world * ext[7] == ext[6] * ext[6])
-        self._shard_mismatch = (~shard_ok if self._shard_mismatch is None else self._shard_mismatch | ~shard_ok)
+        dist.all_reduce(sb["ext"])
+        shard_ok = self._record_agreement(same_on_all_ranks(sb["ext"][4:], world))
         mark()
         fused.shard_backward(sb, b, e)
         mark()
         dist.all_reduce(fused._grad_flat)                              # shards SUM to the full-batch gradient
         fused.shard_update(self.optimizer)
         mark()
-        if prof:
+        report(e - b, M)
+        self._book_step(sb["keys_used"][:M], sb["weights"][:M], sb["g"][:e - b], sb["mine"][:e - b], M, scheduler=True)
+        return sb["counts"][:M], sb["weights"][:M], nan_unless(shard_ok, sb["ev"])
+
+    def _shard_stage_timer(self):
+        """NAQS_SHARD_PROFILE=1 (developer aid): synchronised wall times of the sharded step's five stages.  -> (mark, to be
+        called after every stage; report(rows, M), which prints the running means every 20th step); both do nothing otherwise."""
+        if os.environ.get("NAQS_SHARD_PROFILE") != "1":
+            return (lambda: None), (lambda rows, M: None)
+        torch.cuda.synchronize()
+        t_ = [time.perf_counter()]
+
+        def mark():
+            torch.cuda.synchronize()
+            t_.append(time.perf_counter())
+
+        def report(rows, M):
             acc = self.__dict__.setdefault("_shard_prof", [0.0] * 6)
             for i_ in range(5):
                 acc[i_] += t_[i_ + 1] - t_[i_]
             acc[5] += 1
             if acc[5] % 20 == 0:
                 print("[shard profile] gather %.0f us | eloc+proof %.0f | reduce+check %.0f | backward %.0f | reduce+update %.0f (rows %d of %d)"
-                      % tuple([a_ / acc[5] * 1e6 for a_ in acc[:5]] + [e - b, M]), flush=True)
-        wf.fused_repacked()
-        keys = sb["keys_used"][:M]
-        self._sample_keys, self._sample_weights, self._prefused = keys, sb["weights"][:M], None
-        if self.track_sampled_idxs:
-            self._sampled_ring_off += M
-        self._loss_terms, self._last_loss = (sb["g"][:e - b], sb["mine"][:e - b]), None
-        if self.scheduler is not None:
-            self.scheduler.step()
-        ev = torch.where(shard_ok, sb["ev"], torch.full_like(sb["ev"], float("nan")))
-        return sb["counts"][:M], sb["weights"][:M], ev
+                      % tuple([a_ / acc[5] * 1e6 for a_ in acc[:5]] + [rows, M]), flush=True)
+        return mark, report
 
     def get_samples(self, last_action=0, lazy=False):
         """Adaptive sample count (energy.py:936-971): x10 while too few unique samples, /10 when too many
         or when the unique-prefix tree exceeds ``n_unq_samples_max``.  -> (states, counts, probs); the keys and the
         weights counts / sum(counts) of the same draw are left in ``self._sample_keys`` / ``self._sample_weights``.
         ``lazy`` (the training loop): states come back as ``LazyStates`` (built from the keys only if looked at)."""
-        action = 0
         if self.use_fused:
             # one full re-pack of the parameters now (sampler, forward and backward all read it) instead of an
             # amplitude-only one here and a full one before the forward pass
@@ -1196,18 +1237,8 @@ class PartialSamplingOptimizer(OptimizerBase):
             n_unq, completed = len(states), True
         except MaxBatchSizeExceededError:
             print("MaxBatchSizeExceededError")
-            n_unq, completed, action = self.n_unq_samples_max + 1, False, -1
-        if ((self.n_samples != self.n_unq_samples_min) and (self.n_samples != self.n_samples_max)) or not completed:
-            if n_unq < self.n_unq_samples_min and last_action >= 0:
-                action = 1
-                self.n_samples = int(min(self.n_samples * 10, self.n_samples_max))
-                print(f"\t...{n_unq} unique samples generated --> increasing batch size to "
-                      f"{self.n_samples / 1e6:.1f}M at epoch {self.n_epochs}.")
-            elif n_unq > self.n_unq_samples_max and last_action <= 0:
-                action = -1
-                self.n_samples = int(max(self.n_samples / 10, self.n_unq_samples_min))
-                print(f"\t...{n_unq} unique samples generated --> decreasing batch size to "
-                      f"{self.n_samples / 1e6:.1f}M at epoch {self.n_epochs}.")
+            n_unq, completed = None, False
+        action = self._adapt_n_samples(n_unq, completed, last_action)
         if action != 0:
             return self.get_samples(action, lazy=lazy)
         return states, counts, probs
@@ -1327,16 +1358,10 @@ class PartialSamplingOptimizer(OptimizerBase):
         for step, n_unq, overflow, action, n_samples in res["events"]:
             if overflow:
                 print("MaxBatchSizeExceededError")
-            if action > 0:
-                print(f"\t...{n_unq} unique samples generated --> increasing batch size to "
-                      f"{n_samples / 1e6:.1f}M at epoch {epoch0 + step}.")
-            elif action < 0:
-                print(f"\t...{n_unq} unique samples generated --> decreasing batch size to "
-                      f"{n_samples / 1e6:.1f}M at epoch {epoch0 + step}.")
+            if action != 0:
+                print(self._adapt_message(n_unq, action, n_samples, epoch0 + step))
         self.n_samples = res["n_samples"]
         wf._sample_calls = res["sample_calls"]
-        if self.track_sampled_idxs:
-            self._sampled_ring_off = res["ring_off"]
         done = res["steps"]
         for i in range(done):
             self.n_steps += 1
@@ -1344,10 +1369,9 @@ class PartialSamplingOptimizer(OptimizerBase):
             self._pending_log.append((self.n_steps, res["ev"][i], res["M"][i], run_time0 + res["t"][i]))
         self.run_time = run_time0 + (time.time() - t0)
         if done:
-            wf.fused_repacked()
             self._last_M = res["M"][-1]
-            self._sample_keys, self._sample_weights, self._prefused = res["keys"], res["weights"], None
-            self._loss_terms, self._last_loss = (res["g"], res["log_psi"]), None
+            # (no scheduler: `_can_run_in_library`; the keys of all `done` steps went into the tracking buffer)
+            self._book_step(res["keys"], res["weights"], res["g"], res["log_psi"], res["ring_off"] - off, scheduler=False)
         # failures are raised only now: the `done` steps that finished are applied updates, and the counters above (Adam's step,
         # the sampler's call number, the tracking ring, the log) have to describe the parameters as they are
         if res["error"] is not None:

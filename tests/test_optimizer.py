@@ -158,10 +158,17 @@ def test_two_process_step_below_the_break_even_is_replicated(tmp_path):
 
 
 def test_one_call_loop_adapts_the_sample_count_like_get_samples(tmp_path, monkeypatch, capsys):
-    """`_onecall_step` re-implements get_samples' adaptive rules (energy.py:936-971) around `FusedLogPsi.vmc_step`, which
-    abandons a step when get_samples would have re-sampled.  Scripted sampler outcomes (unique counts / tree overflows as a
-    function of n_samples) drive both: same sequence of sample counts, same messages, same final n_samples."""
+    """get_samples, `_onecall_step` (around `FusedLogPsi.vmc_step`, which abandons a step when get_samples would have
+    re-sampled) and the sharded step (`_resample_until_taken` around its first library call, driven directly here) share one
+    adaptive rule (energy.py:936-971).  Scripted sampler outcomes (unique counts / tree overflows as a function of
+    n_samples) drive all three: same sequence of sample counts, same messages, same final n_samples — and the ones
+    get_samples produced before the rule was shared, recorded in tests/golden/adaptive_sample_count.json (without the
+    recording this would compare one function with itself)."""
+    import json
     from naqs_amd.nade import MaxBatchSizeExceededError
+    with open(os.path.join(GOLDEN, "adaptive_sample_count.json")) as f:
+        recorded = {(r["start"], r["script"]): (r["n_samples_asked"], r["messages"], r["n_samples"]) for r in json.load(f)}
+    assert len(recorded) == 10
 
     def outcome(n_samples, script):
         """-> number of unique samples, or None for a tree overflow"""
@@ -175,9 +182,9 @@ def test_one_call_loop_adapts_the_sample_count_like_get_samples(tmp_path, monkey
         lambda n: 2000,                                                 # fine at once
     ]
     for start in (2000, 10 ** 7):
-        for script in scripts:
+        for script_no, script in enumerate(scripts):
             logs = []
-            for mode in ("get_samples", "onecall"):
+            for mode in ("get_samples", "onecall", "loop"):
                 z, hil, wf, opt = make_opt("LiH", tmp_path / mode, monkeypatch, n_samples=start, n_samples_max=10 ** 9,
                                            n_unq_samples_min=100, n_unq_samples_max=3000)
                 calls = []
@@ -192,6 +199,22 @@ def test_one_call_loop_adapts_the_sample_count_like_get_samples(tmp_path, monkey
                     monkeypatch.setattr(opt.wavefunction, "sample", fake_sample)
                     opt.use_fused = False
                     opt.get_samples(lazy=True)
+                elif mode == "loop":
+                    seeds = []
+                    monkeypatch.setattr(opt.wavefunction, "_next_sample_seed", lambda gen: seeds.append(len(seeds)) or seeds[-1])
+
+                    def attempt(m_lo, seed, slot):
+                        assert seed == len(calls) and slot is None          # one seed per attempt, drawn before it
+                        calls.append(int(opt.n_samples))
+                        m = outcome(int(opt.n_samples), script)
+                        if m is None or m > opt.n_unq_samples_max:
+                            return False, 0, True, None
+                        if m < m_lo or m > opt.n_unq_samples_max:
+                            return False, m, False, None
+                        return True, m, False, ("payload", m)
+                    opt.track_sampled_idxs = False
+                    assert opt._resample_until_taken(attempt) == ("payload", outcome(opt.n_samples, script))
+                    assert len(seeds) == len(calls)
                 else:
                     class Fake:
                         def vmc_step(self, ham, n_samples, seed, max_unique, m_lo, m_hi, adam=None, keys_out=None):
@@ -209,8 +232,65 @@ def test_one_call_loop_adapts_the_sample_count_like_get_samples(tmp_path, monkey
                     opt._onecall_step()
                 out = [l for l in capsys.readouterr().out.splitlines() if "unique samples generated" in l or "MaxBatch" in l]
                 logs.append((calls, out, opt.n_samples))
-            assert logs[0] == logs[1], (start, logs)
+            assert logs[0] == logs[1] == logs[2], (start, logs)
             assert len(logs[0][0]) >= 1
+            assert logs[0] == recorded[(start, script_no)], (start, script_no, logs[0], recorded[(start, script_no)])
+
+
+def test_same_table_proof_is_exact_up_to_the_largest_values_the_callers_produce():
+    """`same_on_all_ranks` on the all-reduced (x, x^2) pairs of 1, 2 and 3 ranks: agreement when every rank contributed the
+    same (M, checksum), disagreement when one rank's M differs by 1, or the Ms agree and one checksum differs by 1.  The
+    callers' values are integers M <= 2^24 - 1 (unique samples) and checksums <= 2^20 - 1 (20 low bits), so the largest
+    number formed is world * sum x^2 <= 3 * 3 * (2^24 - 1)^2 < 2^52 < 2^53: float64 holds every one exactly and the test
+    is of exact arithmetic, not of rounding."""
+    from naqs_amd.optimizer import nan_unless, same_on_all_ranks
+    M_MAX, C_MAX = 2 ** 24 - 1, 2 ** 20 - 1
+    assert 3 * 3 * M_MAX ** 2 < 2 ** 53
+
+    def reduced(contributions):
+        """what the all-reduce of the ranks' (m, m^2, c, c^2) leaves on every rank"""
+        return torch.tensor([[float(m), float(m) * m, float(c), float(c) * c] for m, c in contributions], dtype=torch.float64).sum(0)
+
+    for world in (1, 2, 3):
+        for m, c in ((1, 0), (2, 1), (1000, 12345), (M_MAX, C_MAX), (M_MAX - 1, C_MAX - 1), (M_MAX, 1), (3, C_MAX)):
+            same = [(m, c)] * world
+            ok = same_on_all_ranks(reduced(same), world)
+            assert ok.dtype == torch.bool and ok.dim() == 0 and bool(ok), (world, m, c)
+            for r in range(world if world > 1 else 0):
+                for dm, dc in ((-1, 0), (0, -1), (1, 0), (0, 1)):
+                    if not (0 <= m + dm <= M_MAX and 0 <= c + dc <= C_MAX):
+                        continue
+                    ranks = list(same)
+                    ranks[r] = (m + dm, c + dc)
+                    assert not bool(same_on_all_ranks(reduced(ranks), world)), (world, m, c, r, dm, dc)
+    # three pairs (the replicated steps' proof) and the NaN mask of a failed one
+    six = torch.tensor([7., 49., 5., 25., 3., 9.], dtype=torch.float64)
+    assert bool(same_on_all_ranks(2 * six, 2)) and not bool(same_on_all_ranks(2 * six + torch.tensor([0, 0, 0, 0, 1., 7.]), 2))
+    ev = torch.tensor([-1.5, 0.25], dtype=torch.float64)
+    assert torch.equal(nan_unless(torch.tensor(True), ev), ev) and bool(torch.isnan(nan_unless(torch.tensor(False), ev)).all())
+
+
+def test_flat_gradient_buffer_is_made_once():
+    """`FusedLogPsi._ensure_grad_flat`: the second call returns the same storage and leaves the same per-parameter views
+    (the optimiser's `.grad`s alias them).  A handle cannot be built without a device, so the method runs on a bare
+    instance with the three attributes it reads."""
+    from naqs_amd.fused import FusedLogPsi
+    params = [torch.zeros(3, 4), torch.zeros(5), torch.zeros(2, 1, 2)]
+
+    class Net:
+        def param_list(self):
+            return params
+    f = FusedLogPsi.__new__(FusedLogPsi)
+    f.wf, f.device, f.n_params = Net(), torch.device("cpu"), sum(p.numel() for p in params)
+    f._grad_flat = f._grad_views = None
+    flat = f._ensure_grad_flat()
+    views = list(f._grad_views)
+    assert flat.shape == (f.n_params,) and flat.dtype == torch.float32 and [v.shape for v in views] == [p.shape for p in params]
+    offs = [(v.data_ptr() - flat.data_ptr()) // 4 for v in views]
+    assert offs == [0, 12, 17] and all(v._base is flat for v in views)
+    again = f._ensure_grad_flat()
+    assert again is flat and again.data_ptr() == flat.data_ptr()
+    assert len(f._grad_views) == len(views) and all(a is b for a, b in zip(f._grad_views, views))
 
 
 def _switch_worker(rank, world, port, tmp, out):
