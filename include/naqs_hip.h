@@ -262,6 +262,62 @@ int naqs_ham_eig_lowest(naqs_ham_t *h, int64_t M, const uint64_t *keys_dev, cons
                         int32_t max_products, int32_t m_max, double delta, double *vec_dev /* [M] */,
                         double info_host[4] /* theta, rho, products, status */, void *stream);
 
+/*
+ * The block product: nb (1 .. 8) coefficient vectors on ONE row walk over the M table keys keys_dev.
+ *   C_dev   [nb][M]  vector c is the contiguous row c (real float64)
+ *   num_dev [nb][M]  num[c][i] = sum_{j != i} H_ij C[c][j]
+ *   diag_dev [M]     diag[i] = H_ii                      so that (H C[c])_i = num[c][i] + diag[i] * C[c][i]
+ * Finding the partners of a key and forming H_ij does not depend on the vector, so the walk is made once: the vectors are first
+ * laid out [M][4] (nb <= 4) or [M][8] in the handle's scratch — the padding columns zero —, and a hit reads one contiguous run
+ * and does that many multiply-adds.  Column c of num_dev, and diag_dev, have the bits naqs_ham_pt2 gives with ext_keys_dev =
+ * keys_dev and c_dev = row c, for every nb and every form of the walk (NAQS_STAGE, NAQS_BLOCK, the Bloom filter).
+ * NAQS_ERR_INVALID: a null pointer, M < 1, nb outside 1 .. 8.  NAQS_ERR_UNSUPPORTED: M > 2^24 - 1 (as naqs_ham_pt2).  Nothing
+ * is read back; the scratch grows on demand behind a device synchronisation.  naqs_ham_last_kernel names block_kernel's
+ * instance.  It stands in for no reference code.
+ */
+int naqs_ham_block_product(naqs_ham_t *h, int64_t M, const uint64_t *keys_dev, int32_t nb, const double *C_dev,
+                           double *num_dev, double *diag_dev, void *stream);
+
+/*
+ * The k = min(n_roots, M) lowest eigenpairs of H restricted to the M table keys, by a block Davidson iteration in real float64
+ * with naqs_ham_eig_lowest's correction, tol and delta.  1 <= n_roots <= 8, 2 n_roots <= m_max <= 32; v0_dev [n_roots][M] holds
+ * the starts, row j contiguous (the first k are used); d = diag H.
+ *
+ *   V = []                                      the start: the k rows of v0 in order
+ *   for j < k:  t = v0_j ;  twice: t <- t - V^T (V t) ;  V += [t / |t|]
+ *               |t| zero, not finite, or <= 1e-14 * its norm before the passes   -> NAQS_ERR_INVALID, no product is run
+ *   W = H V ;  products = k
+ *   repeat
+ *       G = V W^T (upper triangle, mirrored) ;  its k lowest pairs (theta_j, s_j), theta ascending, equal ones by index
+ *       x_j = s_j V ;  y_j = s_j W ;  r_j = y_j - theta_j x_j ;  rho_j = |r_j|
+ *       open = [j : not rho_j < tol * max(1, |theta_j|)], ascending
+ *       open empty -> status 0 ;  m == M -> status 2 ;  products >= max_products -> status 1
+ *       m + len(open) > m_max: restart          V <- [x_j / |x_j|], W <- [y_j / |x_j|], j < k ;  m = k
+ *       for j in open while m < M:
+ *           t = -r_j / max(d - theta_j, delta)                     the positive form, for every root
+ *           twice: t <- t - V^T (V t)                              V includes the vectors accepted earlier in this loop
+ *           |t| not finite, or <= 1e-14 * its norm before the passes: skip this j
+ *           V += [t / |t|] ;  W += [H t / |t|] ;  m += 1 ;  products += 1
+ *       nothing accepted -> status 3
+ *   return theta[k], x_j / |x_j|, rho[k], products, status
+ *
+ * With k = 1 this is naqs_ham_eig_lowest's rule.  Every loop iteration runs ONE block product (naqs_ham_block_product's walk,
+ * the key table built once per call) over the corrections it accepted.  As in naqs_ham_eig_lowest the device forms (H t) / |t|,
+ * keeps x_j and y_j at a restart without the division by |x_j| = 1 + O(2^-52) and sets G after a restart to diag(theta_j); a
+ * correction accepted earlier in the loop is taken out of a later one as t_a (t_a . t) / |t_a|^2: each differs from the rule
+ * by roundings only.  Every sum over M runs in one fixed order: the same bits on repetition and under every form of the walk.
+ * vecs_dev [k][M] receives x_j / |x_j|; theta_host [k], rho_host [k] and info_host [2] = products, status are host memory.
+ * The call synchronises the stream once per loop iteration (64 words are read back: the status and the accepted set) and once
+ * for the start.  Scratch — (2 m_max + 4 k + 1) vectors of M doubles, and the block product's — belongs to the handle.
+ * NAQS_ERR_INVALID: M < 1, a null pointer, tol or delta not positive and finite, n_roots outside 1 .. 8, m_max outside
+ * 2 n_roots .. 32, max_products < 1, or a start that is rank-deficient, zero or not finite (found on the device; no product
+ * is run and vecs_dev is untouched).  NAQS_ERR_UNSUPPORTED: M > 2^24 - 1.  It stands in for no reference code.
+ */
+int naqs_ham_eig_lowest_k(naqs_ham_t *h, int64_t M, const uint64_t *keys_dev, int32_t n_roots, const double *v0_dev, double tol,
+                          int32_t max_products, int32_t m_max, double delta, double *vecs_dev /* [k][M] */,
+                          double *theta_host /* [k] */, double *rho_host /* [k] */, int32_t info_host[2] /* products, status */,
+                          void *stream);
+
 /* ---- inner ring: device versions of the three Cython entry points the reference imports ---- */
 
 /* src.utils.hamiltonian_math.popcount_parity (hamiltonian_math.pyx:455-484):

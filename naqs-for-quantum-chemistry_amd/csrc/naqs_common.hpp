@@ -117,15 +117,21 @@ void ham_set_last_kernel(naqs_ham *h, const char *name);
 // the small problem, one array grown there on demand, freed by naqs_ham_destroy).  ham_eig_begin builds the key table of one
 // solve; ham_eig_product launches the row walk of naqs_ham_pt2 on it, the rows being the table's own keys:
 // num_i = sum_{j != i} H_ij v_j and diag_i = H_ii, so H v = num + diag * v.
+// ham_eig_block_product (naqs_ham_block_product, naqs_ham_eig_lowest_k) is that product for nb <= 8 vectors on one walk: vector
+// c is src[slots[c] * ld + i], num[c * ldn + i] its product; the vectors are first laid out [M][4 or 8] in `pack`.
 struct EigScratch {
     double *buf = nullptr;
     int64_t doubles = 0;
+    double *pack = nullptr;
+    int64_t pack_doubles = 0;
 };
 EigScratch *ham_eig_scratch(naqs_ham *h);
 const char *ham_last_kernel_name(const naqs_ham *h);
 int ham_eig_begin(naqs_ham *h, int64_t M, const uint64_t *keys_dev, hipStream_t s, ElocFeed *feed);
 int ham_eig_product(naqs_ham *h, int64_t M, const uint64_t *keys_dev, const ElocFeed &feed, const double *v_dev, double *num_dev,
                     double *diag_dev, hipStream_t s);
+int ham_eig_block_product(naqs_ham *h, int64_t M, const uint64_t *keys_dev, const ElocFeed &feed, int nb, const double *src_dev,
+                          int64_t ld, const int32_t *slots, double *num_dev, int64_t ldn, double *diag_dev, hipStream_t s);
 int net_device(const naqs_net *n);           // implemented in naqs_logpsi.hip
 
 }  // namespace naqs

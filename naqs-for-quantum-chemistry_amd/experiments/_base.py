@@ -63,6 +63,8 @@ _VALUE_FLAGS = [
     (("-eig_solver",), "eig_solver", dict(type=str, choices=["lanczos", "davidson"],
                                           help="The sampled-subspace diagonalisations (also -pt2's and -sci's) by Lanczos (the default) or by "
                                                "the Davidson solver of naqs_ham_eig_lowest.")),
+    (("-roots",), "roots", dict(type=int, help="After everything else, the K (1..8) lowest states of the sampled subspace from a draw of "
+                                              "its own, by the block Davidson solver; with -pt2 each with its own correction.")),
 ]
 # (flags, dest, default expression on the get_parser keywords, help)
 _SWITCHES = [
@@ -97,7 +99,7 @@ _DEFAULTS = dict(molecule="molecules/H2", hamiltonian_fname=None, out=None, numb
                  use_amp_spin_sym=True, use_phase_spin_sym=False, aggregate_phase=True, restrict_H=True,
                  reset_opt=False, verbose=False, seed=-1, exact_eloc=False, train_exact_eloc=False,
                  sr=False, sr_shift=1e-3, sr_lr=0.1, sr_solver=None, sr_momentum=0.0, pt2=False, sci=0, sci_grow=None, sci_start=None,
-                 eig_solver=None)
+                 eig_solver=None, roots=None)
 
 
 def get_parser(**overrides):
@@ -196,8 +198,9 @@ def _run(molecule_fname, hamiltonian_fname, exp_name, num_experiments, pretraine
          n_layer_phase, n_excitations_max, comb_amp_phase, use_amp_spin_sym, use_phase_spin_sym, aggregate_phase,
          use_restrictedH, loadH, presolveH, overwrite_pauli_hamiltonian, verbose, seed, device=None, exact_eloc=False,
          train_exact_eloc=False, sr=False, sr_shift=1e-3, sr_lr=0.1, sr_solver=None, sr_momentum=0.0, pt2=False,
-         sci=0, sci_grow=None, sci_start=None, eig_solver=None):
+         sci=0, sci_grow=None, sci_start=None, eig_solver=None, roots=None):
     _check_sci(sci, sci_grow, sci_start)
+    _check_roots(roots)
     if sr_solver is not None and not sr:
         raise ValueError("-sr_solver chooses the solver of -sr (natural gradient): give -sr as well")
     if sr_momentum and not sr:
@@ -228,7 +231,8 @@ def _run(molecule_fname, hamiltonian_fname, exp_name, num_experiments, pretraine
                            dict(dict(diag_shift=sr_shift, lr=sr_lr), **({} if sr_solver is None else dict(solver=sr_solver)),
                                 **(dict(momentum=sr_momentum) if sr_momentum else {})) if sr else None, **(dict(pt2=True) if pt2 else {}),
                            **(dict(sci=dict(n_iter=int(sci), grow=1.0 if sci_grow is None else float(sci_grow), n_start=sci_start)) if sci else {}),
-                           **({} if eig_solver is None else dict(eig_solver=eig_solver)))
+                           **({} if eig_solver is None else dict(eig_solver=eig_solver)),
+                           **({} if roots is None else dict(roots=int(roots))))
     finally:
         if locked[0]:
             _SETUP_LOCK.release()
@@ -241,7 +245,8 @@ def _run_locked(locked, molecule_fname, hamiltonian_fname, exp_name, num_experim
                 reset_optimizer, qubit_ordering, masking, lr, lr_lut, n_samps, n_samps_max, n_unq_samps_min, n_unq_samps_max,
                 n_train, n_pretrain, output_freq, save_freq, n_lut, n_hid, n_layer, n_hid_phase, n_layer_phase, comb_amp_phase,
                 use_amp_spin_sym, use_phase_spin_sym, aggregate_phase, use_restrictedH, presolveH, verbose, seed, device,
-                exact_eloc=False, train_exact_eloc=False, natural_gradient=None, pt2=False, sci=None, eig_solver=None):
+                exact_eloc=False, train_exact_eloc=False, natural_gradient=None, pt2=False, sci=None, eig_solver=None,
+                roots=None):
     seed = set_global_seed(_agree_on_seed(seed))
     molecule, qubit_hamiltonian = load_molecule(molecule_fname, hamiltonian_fname=hamiltonian_fname, verbose=True)
     N = molecule.n_qubits
@@ -342,8 +347,10 @@ def _run_locked(locked, molecule_fname, hamiltonian_fname, exp_name, num_experim
         eig_val, _, n_unq = (sub["eig"], sub["vec0"], sub["n_unq"]) if sub is not None else opt.solve_H(n_samps=opt.n_samples, ret_n_samps=True)
         # -exact_eloc: the trained state's energy from a fresh draw with psi evaluated on every connected state
         exact = opt.evaluate_energy(n_samps=opt.n_samples, exact=True) if exact_eloc else None
+        # -roots: the lowest states of the sampled subspace, from a draw of its own, after everything above
+        rooted = opt.solve_H_roots(n_samps=opt.n_samples, n_roots=roots, pt2=bool(pt2)) if roots else None
         results.append(_summarise(opt, molecule, exp_name_i, eig_val, n_unq, train_time, exact=exact, **(dict(pt2=sub) if pt2 else {}),
-                                  **(dict(sci=grown) if grown is not None else {})))
+                                  **(dict(sci=grown) if grown is not None else {}), **(dict(roots=rooted) if rooted is not None else {})))
     return results
 
 
@@ -360,6 +367,18 @@ def _check_sci(sci, sci_grow, sci_start):
         raise ValueError("-sci_start must be at least 1")
 
 
+def _check_roots(roots):
+    if roots is not None and not 1 <= roots <= 8:
+        raise ValueError("-roots takes the number of lowest states of the sampled subspace, 1..8")
+
+
+def _roots_lines(roots):
+    """summary.txt's lines of a -roots run: one per root — its index, its energy, its gap to root 0 and, with -pt2, E_j + E_PT2,j."""
+    e = roots["eigs"]
+    return [f"sampled-subspace root {j} ({roots['n_unq']} states) : {e[j]:.8f} , gap to root 0 {(e[j] - e[0]) * 1e3:.4f} mHa" +
+            (f" , E + E_PT2 {e[j] + roots['e_pt2'][j]:.8f}" if "e_pt2" in roots else "") for j in range(len(e))]
+
+
 def _sci_lines(sci, fci):
     """summary.txt's lines of a selected-CI run: one per iteration, the extrapolation, the stop reason."""
     lines = []
@@ -374,7 +393,7 @@ def _sci_lines(sci, fci):
     return lines
 
 
-def _summarise(opt, molecule, exp_name, eig_val, n_unq, train_time, exact=None, pt2=None, sci=None):
+def _summarise(opt, molecule, exp_name, eig_val, n_unq, train_time, exact=None, pt2=None, sci=None, roots=None):
     """summary.txt next to the checkpoints (the reference's _base.py:330-390, same quantities)."""
     e = np.array([x[1] for x in opt.log[LogKey.E_LOC]])
     window = min(50, len(e))
@@ -409,6 +428,9 @@ def _summarise(opt, molecule, exp_name, eig_val, n_unq, train_time, exact=None, 
     if sci is not None:
         lines.extend(_sci_lines(sci, fci))
         res.update(sci_history=sci["history"], sci_extrapolated=sci["extrapolated"], sci_stopped=sci["stopped"])
+    if roots is not None:
+        lines.extend(_roots_lines(roots))
+        res.update(roots=roots["eigs"], **(dict(roots_e_pt2=roots["e_pt2"]) if "e_pt2" in roots else {}))
     mk_dir(opt.save_loc, quiet=True)
     with open(os.path.join(opt.save_loc, "summary.txt"), "w") as f:
         f.write("\n".join(lines) + "\n")
@@ -516,6 +538,7 @@ def run_from_parser(parser, argv=None):
     if args.sr_momentum and not args.sr:
         raise ValueError("-sr_momentum sets the momentum of -sr (natural gradient): give -sr as well")
     _check_sci(args.sci, args.sci_grow, args.sci_start)
+    _check_roots(args.roots)
     if args.farm and "WORLD_SIZE" not in os.environ and (args.per_gpu > 1 or args.seeds or args.farm_gpus > 0):
         return _farm_launch(args, argv)
     rank, world = _setup_distributed(args.farm, args.per_gpu)
@@ -551,7 +574,7 @@ def _run_job(args, molecule_fname, seed):
             continue
         if (key == "sr_solver" and val is None) or (key == "sr_momentum" and not val):
             continue
-        if (key == "sci" and not val) or (key in ("sci_grow", "sci_start", "eig_solver") and val is None):
+        if (key == "sci" and not val) or (key in ("sci_grow", "sci_start", "eig_solver", "roots") and val is None):
             continue
         print(f"\t{key} : {val}")
     print("")
@@ -573,7 +596,8 @@ def _run_job(args, molecule_fname, seed):
                 **(dict(sr_momentum=args.sr_momentum) if args.sr_momentum else {}), **(dict(pt2=True) if args.pt2 else {}),
                 **(dict(sci=args.sci) if args.sci else {}), **({} if args.sci_grow is None else dict(sci_grow=args.sci_grow)),
                 **({} if args.sci_start is None else dict(sci_start=args.sci_start)),
-                **({} if args.eig_solver is None else dict(eig_solver=args.eig_solver)))
+                **({} if args.eig_solver is None else dict(eig_solver=args.eig_solver)),
+                **({} if args.roots is None else dict(roots=args.roots)))
 
 
 def run(*args, **kwargs):

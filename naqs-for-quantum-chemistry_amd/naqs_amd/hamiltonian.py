@@ -40,6 +40,7 @@ class DevicePauliHamiltonian:
         self._h = ctypes.c_void_p(None)
         self.last_lanczos_iterations = 0          # products of the most recent lowest_eigenpair call (measurement aid)
         self.last_eig_info = None                 # dict(products, residual, status) of the most recent solver="davidson" call
+                                                  # (lowest_eigenpairs: residuals, one per root)
         self._lib = _lib.load_library()           # raises NaqsError when the HIP library is missing
         if not torch.cuda.is_available():
             raise _lib.NaqsError("DevicePauliHamiltonian needs a HIP device (no CPU fallback)")
@@ -305,6 +306,65 @@ class DevicePauliHamiltonian:
         self.last_lanczos_iterations = int(info[2])
         self.last_eig_info = dict(products=int(info[2]), residual=float(info[1]), status=int(info[3]))
         return float(info[0]), vec
+
+    # ---- several vectors on one row walk; the k lowest roots -------------------------------------
+    def block_product(self, keys, C):
+        """``naqs_ham_block_product``: for the nb (1..8) rows of ``C`` [nb, M] (real float64) num[c, i] = sum_{j != i} H_ij C[c, j]
+        over the table ``keys`` and diag[i] = H_ii, in ONE row walk — H C[c] = num[c] + diag * C[c].
+        -> (num [nb, M], diag [M]) float64 device tensors."""
+        M = keys.shape[0]
+        if not (keys.is_cuda and keys.dtype == torch.int64):
+            raise ValueError("keys must be an int64 device tensor")
+        C = C.to(device=self.device, dtype=torch.float64).contiguous()
+        if C.dim() != 2 or C.shape[1] != M or not 1 <= C.shape[0] <= 8:
+            raise ValueError(f"C must have shape [1..8, {M}], got {tuple(C.shape)}")
+        nb = C.shape[0]
+        num = torch.empty((nb, M), dtype=torch.float64, device=self.device)
+        diag = torch.empty(M, dtype=torch.float64, device=self.device)
+        st = self._lib.naqs_ham_block_product(self._h, M, keys.contiguous().data_ptr(), nb, C.data_ptr(), num.data_ptr(), diag.data_ptr(),
+                                              _stream_ptr(self.device))
+        _lib.check(st, "naqs_ham_block_product")
+        return num, diag
+
+    @torch.no_grad()
+    def lowest_eigenpairs(self, keys, k, max_iter=400, tol=1e-10, seed=0, v0=None, m_max=32, delta=1e-2):
+        """The k' = min(k, M) lowest eigenpairs of H restricted to the sampled keys by the block Davidson iteration of the library
+        (``naqs_ham_eig_lowest_k``: one block product per iteration).  1 <= k <= 8; ``max_iter`` bounds the products, ``m_max``
+        (2 k .. 32) the basis, ``delta`` floors the preconditioner, as ``lowest_eigenpair(solver="davidson")``.  ``v0``: the starts
+        [k, M]; ``None``: k draws of the seeded generator, row 0 the vector ``lowest_eigenpair`` draws.  H on the keys must be
+        symmetric.  -> (theta float64 ndarray [k'] ascending, vecs float64 device tensor [k', M], rows of norm 1);
+        ``last_eig_info = dict(products, residuals, status)`` (status as ``lowest_eigenpair``; 3: no correction was accepted)."""
+        M = keys.shape[0]
+        k, max_iter, m_max, tol, delta = int(k), int(max_iter), int(m_max), float(tol), float(delta)
+        if M == 0:
+            raise ValueError("empty sample set")
+        if not 1 <= k <= 8:
+            raise ValueError(f"k must lie in 1..8, got {k}")
+        if not 2 * k <= m_max <= 32:
+            raise ValueError(f"m_max must lie in 2 k..32 = {2 * k}..32, got {m_max}")
+        if max_iter < 1 or not (np.isfinite(tol) and tol > 0 and np.isfinite(delta) and delta > 0):
+            raise ValueError("max_iter must be at least 1, tol and delta positive and finite")
+        if not (keys.is_cuda and keys.dtype == torch.int64):
+            raise ValueError("keys must be an int64 device tensor")
+        kk = min(k, M)
+        if v0 is None:
+            gen = torch.Generator(device=self.device).manual_seed(int(seed))
+            v = torch.stack([torch.randn(M, dtype=torch.float64, device=self.device, generator=gen) for _ in range(k)])
+        else:
+            v = v0.to(device=self.device, dtype=torch.float64).contiguous()
+            if v.shape != (k, M):
+                raise ValueError(f"v0 must have shape [{k}, {M}], got {tuple(v.shape)}")
+        keys = keys.contiguous()
+        vecs = torch.empty((kk, M), dtype=torch.float64, device=self.device)
+        theta, rho, info = (ctypes.c_double * kk)(), (ctypes.c_double * kk)(), (ctypes.c_int32 * 2)()
+        st = self._lib.naqs_ham_eig_lowest_k(self._h, M, keys.data_ptr(), k, v.data_ptr(), tol, max_iter, m_max, delta, vecs.data_ptr(),
+                                             theta, rho, info, _stream_ptr(self.device))
+        if st == -1:                              # NAQS_ERR_INVALID: every other argument was checked above
+            raise ValueError(f"v0 must hold {kk} finite, linearly independent rows of shape [{M}]")
+        _lib.check(st, "naqs_ham_eig_lowest_k")
+        self.last_lanczos_iterations = int(info[0])
+        self.last_eig_info = dict(products=int(info[0]), residuals=[float(r) for r in rho], status=int(info[1]))
+        return np.array(list(theta), np.float64), vecs
 
     # ---- Epstein-Nesbet second-order correction of a subspace energy -----------------------------
     def pt2(self, keys, c, e0, ext_keys, rows=False):

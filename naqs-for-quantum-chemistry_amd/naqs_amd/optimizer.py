@@ -1297,6 +1297,26 @@ class PartialSamplingOptimizer(OptimizerBase):
         return dict(eig=val, vec0=abs(float(vec[0])), n_unq=n_unq, e_pt2=pt2["e_pt2"], n_external=pt2["n_external"],
                     n_intruders=pt2["n_intruders"])
 
+    def solve_H_roots(self, n_samps=None, n_roots=2, pt2=False):
+        """The ``n_roots`` (1..8) lowest eigenpairs of H restricted to solve_H's sample — one draw — by the block Davidson solver
+        (DevicePauliHamiltonian.lowest_eigenpairs); with ``pt2`` each root's own Epstein-Nesbet correction on the same keys
+        (pt2_correction(keys, vecs[j], e0=eigs[j])).  Every eigs[j] is variational for the j-th state of the sampled space;
+        eigs[j] + e_pt2[j] is not.  A sample of fewer states than n_roots returns that many roots.
+        -> dict(keys, eigs, vec0s, n_unq[, e_pt2, n_external, n_intruders: one entry per root]).  Device only."""
+        if not 1 <= int(n_roots) <= 8:
+            raise ValueError(f"n_roots must lie in 1..8, got {n_roots}")
+        if self.device.type != "cuda":
+            raise NotImplementedError("solve_H_roots runs on the HIP kernels (naqs_ham_eig_lowest_k): there is no CPU form")
+        keys, n_unq = self._solve_H_keys(n_samps)
+        keys_dev = keys_to_device(keys, self.device)
+        eigs, vecs = self.pauli_hamiltonian.lowest_eigenpairs(keys_dev, int(n_roots))
+        res = dict(keys=keys_dev, eigs=[float(e) for e in eigs], vec0s=[abs(float(v)) for v in vecs[:, 0]], n_unq=n_unq)
+        if pt2:
+            rows = [self.pauli_hamiltonian.pt2_correction(keys_dev, vecs[j], e0=res["eigs"][j]) for j in range(len(res["eigs"]))]
+            res.update(e_pt2=[r["e_pt2"] for r in rows], n_external=[r["n_external"] for r in rows],
+                       n_intruders=[r["n_intruders"] for r in rows])
+        return res
+
     def solve_H_sci(self, n_samps=None, n_iter=4, grow=1.0, n_start=None, **kwargs):
         """Selected CI from solve_H's sample (DevicePauliHamiltonian.selected_ci): ``n_iter`` iterations, each growth step
         adding the ceil(grow M) connected states of largest second-order importance.  ``n_start`` cuts the draw to its
