@@ -318,6 +318,44 @@ int naqs_ham_eig_lowest_k(naqs_ham_t *h, int64_t M, const uint64_t *keys_dev, in
                           double *theta_host /* [k] */, double *rho_host /* [k] */, int32_t info_host[2] /* products, status */,
                           void *stream);
 
+/*
+ * naqs_ham_pt2 for nb (1 .. 8) vectors of one table on ONE walk over the external rows: C_dev [nb][M] (row c contiguous, as
+ * naqs_ham_block_product takes it) with the energies e_host [nb] (host memory); num_dev [nb][n_ext] (leading dimension n_ext)
+ * and diag_dev [n_ext], both optional; out4_dev [nb][4] (mandatory).  Finding a row's partners and forming H[a, j] does not
+ * depend on the vector, so the rows of all nb vectors come from one launch of naqs_ham_block_product's walk, its row list the
+ * external keys, and their sums from one launch that reads diag once per row.
+ * Row c of num_dev, diag_dev and out4_dev[c] have exactly the bits naqs_ham_pt2(h, M, keys_dev, C_dev[c], e_host[c], n_ext,
+ * ext_keys_dev, ...) writes, for every nb and every form of the walk (NAQS_STAGE, NAQS_BLOCK, the Bloom filter); the key table
+ * is built once per call.  Null num_dev / diag_dev: the handle's own scratch — naqs_ham_pt2's pair of arrays, grown as there.
+ * n_ext = 0: out4 = 0, NAQS_OK.  nb outside 1 .. 8, M < 1, n_ext < 0, a null required pointer or a non-finite e_host[c]:
+ * NAQS_ERR_INVALID.  M > 2^24 - 1 or n_ext > 2^30: NAQS_ERR_UNSUPPORTED.  naqs_ham_last_kernel names block_kernel's instance.
+ * It stands in for no reference code.
+ */
+int naqs_ham_pt2_block(naqs_ham_t *h, int64_t M, const uint64_t *keys_dev, int32_t nb, const double *C_dev /* [nb][M] */,
+                       const double *e_host /* [nb] */, int64_t n_ext, const uint64_t *ext_keys_dev,
+                       double *num_dev /* [nb][n_ext], optional */, double *diag_dev /* [n_ext], optional */,
+                       double *out4_dev /* [nb][4] */, void *stream);
+
+/*
+ * Selected CI for several roots: naqs_ham_pt2_select with the importances of nb (1 .. 8) roots averaged.  num_dev [nb][n_ext]
+ * (leading dimension n_ext) and diag_dev [n_ext] are what naqs_ham_pt2_block writes; e_host [nb] and w_host [nb] (host memory)
+ * the roots' energies and weights.  The rule, every operation one float64 rounding, no product and sum contracted:
+ *   a root with w_j == 0 is skipped entirely (its row of num and its energy are never read); the others are LIVE, in ascending j;
+ *   for each live j:  den_ja = diag_a - e_j ;  q_ja = (num_ja * num_ja) / den_ja;
+ *   a is an INTRUDER if !(den_ja > 0) or num_ja is NaN for ANY live j, and then eps_a = +inf;
+ *   otherwise eps_a = w_j0 * q_j0a for the first live root, then eps_a = eps_a + w_j * q_ja for each further live root in order.
+ * Eligibility, tau, cut, the group at the cut that is never split, the row order of out_keys_dev, count_dev[2], overflow and
+ * capacity are naqs_ham_pt2_select's, as are its two kernel forms (NAQS_SELECT_FORM), its scratch and its refusals;
+ * NAQS_ERR_INVALID in addition for nb outside 1 .. 8, a weight that is negative or not finite, no live root, or a non-finite
+ * e_j of a live root.
+ * With nb = 1 and w = [1] the call selects exactly what naqs_ham_pt2_select selects, with the same counts (1 * q is exact);
+ * with w = [1, 0, ...] what the single-root call on row 0 selects.  It stands in for no reference code.
+ */
+int naqs_ham_pt2_select_avg(naqs_ham_t *h, int64_t n_ext, const uint64_t *ext_keys_dev, int32_t nb, const double *num_dev,
+                            const double *diag_dev, const double *e_host /* [nb] */, const double *w_host /* [nb] */, int64_t k,
+                            double eps_min, double tie_rtol, int64_t capacity, uint64_t *out_keys_dev,
+                            int64_t *count_dev /* [2] */, void *stream);
+
 /* ---- inner ring: device versions of the three Cython entry points the reference imports ---- */
 
 /* src.utils.hamiltonian_math.popcount_parity (hamiltonian_math.pyx:455-484):

@@ -14,6 +14,10 @@
 // Two forms.  ONE: a single 1 024-thread workgroup does the eight passes and the ordered compaction in one launch, histograms
 // in LDS only, no scratch.  MULTI: tiles of 2 048 rows, one 256-thread workgroup each; a memset, eight histogram launches, a
 // counts launch, a one-workgroup scan and the scatter.  The crossover is measured (tools/sci_bench.py, profiles/sci.txt).
+//
+// naqs_ham_pt2_select_avg (selected CI for several roots) is the same call with another importance: the kernels
+// that read rows are templates on their argument struct, and only row_key differs between SelArgs and SelAvgArgs.  The SelArgs
+// instances have the device code they had before they were templates (tools/kernel_asm_diff.py).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -50,6 +54,42 @@ __device__ __forceinline__ uint64_t row_key(const SelArgs &a, const int64_t i, d
     const double num = a.num[i], den = a.diag[i] - a.e0;
     const bool intr = !(den > 0) || num != num;
     const double e = intr ? __builtin_inf() : (num * num) / den;
+    *eps = e;
+    *intruder = intr;
+    return (e > 0 && e >= a.eps_min) ? (uint64_t)__double_as_longlong(e) : 0ull;
+}
+
+// naqs_ham_pt2_select_avg: the same call with the importances of several roots averaged.  Only the live roots (w != 0) travel,
+// in ascending order: their columns of num [nb][n], energies and weights.  Every field the kernels share with SelArgs has its name.
+constexpr int MAX_ROOTS = 8;
+struct SelAvgArgs {
+    int64_t n;
+    const uint64_t *keys;
+    const double *num, *diag;        // num [nb][n]
+    double e[MAX_ROOTS], w[MAX_ROOTS];
+    int32_t col[MAX_ROOTS], n_live;
+    double eps_min, factor;
+    int64_t k;
+    int64_t capacity;
+    uint64_t *out;
+    int64_t *count;
+};
+
+// eps_a = w_0 q_0 + w_1 q_1 + ... over the live roots in order, q_j = (num_ja * num_ja) / (diag_a - e_j), each operation one
+// rounding (the library is compiled without contraction); an intruder of ANY live root makes the row one
+__device__ __forceinline__ uint64_t row_key(const SelAvgArgs &a, const int64_t i, double *eps, bool *intruder) {
+    const double dg = a.diag[i];
+    bool intr = false;
+    double e = 0.0;
+#pragma unroll
+    for (int j = 0; j < MAX_ROOTS; ++j) {
+        if (j >= a.n_live) break;
+        const double num = a.num[(size_t)a.col[j] * (size_t)a.n + i], den = dg - a.e[j];
+        intr = intr || !(den > 0) || num != num;
+        const double t = a.w[j] * ((num * num) / den);
+        e = j == 0 ? t : e + t;
+    }
+    if (intr) e = __builtin_inf();
     *eps = e;
     *intruder = intr;
     return (e > 0 && e >= a.eps_min) ? (uint64_t)__double_as_longlong(e) : 0ull;
@@ -114,7 +154,8 @@ __device__ __forceinline__ void chunk_offsets(const bool flag, uint32_t *s_w, ui
 }
 
 // ---- form ONE ----------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(ONE_BLOCK) void select_one_kernel(const SelArgs a) {
+template <typename A>
+__global__ __launch_bounds__(ONE_BLOCK) void select_one_kernel(const A a) {
     __shared__ uint32_t s_hist[BINS];
     __shared__ uint32_t s_w[ONE_BLOCK / WAVE];
     __shared__ uint32_t s_pick[2], s_elig, s_intr;
@@ -185,7 +226,8 @@ __device__ __forceinline__ void derive_prefix(const uint32_t *ghist, const int p
 }
 
 // pass p: rows whose key starts with the prefix of passes 0 .. p-1 into hist[p]
-__global__ __launch_bounds__(MULTI_BLOCK) void select_hist_kernel(const SelArgs a, uint32_t *ghist, const int p) {
+template <typename A>
+__global__ __launch_bounds__(MULTI_BLOCK) void select_hist_kernel(const A a, uint32_t *ghist, const int p) {
     __shared__ uint32_t s_hist[BINS];
     __shared__ unsigned long long s_prefix;
     __shared__ uint32_t s_elig;
@@ -222,7 +264,8 @@ __global__ __launch_bounds__(MULTI_BLOCK) void select_hist_kernel(const SelArgs 
 }
 
 // the cut of a call, from the eight merged histograms (wave 0) -> LDS
-__device__ __forceinline__ void derive_cut(const SelArgs &a, const uint32_t *ghist, double *s_cut, int *s_mode) {
+template <typename A>
+__device__ __forceinline__ void derive_cut(const A &a, const uint32_t *ghist, double *s_cut, int *s_mode) {
     if (threadIdx.x < WAVE) {
         uint64_t pre;
         uint32_t kl;
@@ -236,7 +279,8 @@ __device__ __forceinline__ void derive_cut(const SelArgs &a, const uint32_t *ghi
 }
 
 // selected rows and selected intruders of every tile
-__global__ __launch_bounds__(MULTI_BLOCK) void select_count_kernel(const SelArgs a, const uint32_t *ghist, uint32_t *wg_cnt, uint32_t *wg_intr) {
+template <typename A>
+__global__ __launch_bounds__(MULTI_BLOCK) void select_count_kernel(const A a, const uint32_t *ghist, uint32_t *wg_cnt, uint32_t *wg_intr) {
     __shared__ double s_cut;
     __shared__ int s_mode;
     __shared__ uint32_t s_n[2];
@@ -299,7 +343,8 @@ __global__ __launch_bounds__(ONE_BLOCK) void select_scan_kernel(const int64_t n_
     if (t == 0) { count[0] = (int64_t)base; count[1] = (int64_t)s_intr; }
 }
 
-__global__ __launch_bounds__(MULTI_BLOCK) void select_scatter_kernel(const SelArgs a, const uint32_t *ghist, const uint32_t *wg_off) {
+template <typename A>
+__global__ __launch_bounds__(MULTI_BLOCK) void select_scatter_kernel(const A a, const uint32_t *ghist, const uint32_t *wg_off) {
     __shared__ double s_cut;
     __shared__ int s_mode;
     __shared__ uint32_t s_w[MULTI_BLOCK / WAVE];
@@ -332,6 +377,37 @@ __global__ __launch_bounds__(MULTI_BLOCK) void select_scatter_kernel(const SelAr
 // (the rounds' spread) at 14 336, behind by 5.5 us at 16 384.
 constexpr int64_t ONE_MAX_ROWS = 12288;
 
+// the launches of one call, for either argument struct (the checks are the callers')
+template <typename A>
+int launch_select(naqs_ham_t *h, const A &a, hipStream_t s) {
+    const int64_t n_ext = a.n;
+    const int force = env_int("NAQS_SELECT_FORM", 0);       // tuning/testing: 0 auto, 1 one workgroup, 2 multi
+    const bool one = force == 1 || (force != 2 && n_ext <= ONE_MAX_ROWS);
+    char name[96];
+    if (one) {
+        NAQS_KLAUNCH(select_one_kernel<A>, dim3(1), dim3(ONE_BLOCK), 0, s, a);
+        std::snprintf(name, sizeof(name), "select_one_kernel");
+    } else {
+        const int64_t n_wg = (n_ext + MULTI_TILE - 1) / MULTI_TILE;
+        SelectScratch *sc = ham_select_scratch(h);
+        if (n_wg > sc->tiles) {
+            const int64_t cap = head_room(n_wg, 64);
+            const int st = regrow(sc->words, sc->tiles, cap, ((size_t)HIST_WORDS + 3 * (size_t)cap) * sizeof(uint32_t));
+            if (st != NAQS_OK) return st;
+        }
+        uint32_t *ghist = sc->words, *wg_cnt = ghist + HIST_WORDS, *wg_intr = wg_cnt + sc->tiles, *wg_off = wg_intr + sc->tiles;
+        HIP_TRY(hipMemsetAsync(ghist, 0, HIST_WORDS * sizeof(uint32_t), s));
+        for (int p = 0; p < DIGITS; ++p) NAQS_KLAUNCH(select_hist_kernel<A>, dim3((unsigned)n_wg), dim3(MULTI_BLOCK), 0, s, a, ghist, p);
+        NAQS_KLAUNCH(select_count_kernel<A>, dim3((unsigned)n_wg), dim3(MULTI_BLOCK), 0, s, a, ghist, wg_cnt, wg_intr);
+        NAQS_KLAUNCH(select_scan_kernel, dim3(1), dim3(ONE_BLOCK), 0, s, n_wg, wg_cnt, wg_intr, wg_off, a.count);
+        NAQS_KLAUNCH(select_scatter_kernel<A>, dim3((unsigned)n_wg), dim3(MULTI_BLOCK), 0, s, a, ghist, wg_off);
+        std::snprintf(name, sizeof(name), "select_hist_kernel x8 + select_count_kernel + select_scan_kernel + select_scatter_kernel");
+    }
+    HIP_TRY(hipGetLastError());
+    ham_set_last_kernel(h, name);
+    return NAQS_OK;
+}
+
 }  // namespace
 
 NAQS_API int naqs_ham_pt2_select(naqs_ham_t *h, int64_t n_ext, const uint64_t *ext_keys_dev, const double *num_dev, const double *diag_dev,
@@ -350,30 +426,36 @@ NAQS_API int naqs_ham_pt2_select(naqs_ham_t *h, int64_t n_ext, const uint64_t *e
         HIP_TRY(hipMemsetAsync(count_dev, 0, 2 * sizeof(int64_t), s));
         return NAQS_OK;
     }
-    const int force = env_int("NAQS_SELECT_FORM", 0);       // tuning/testing: 0 auto, 1 one workgroup, 2 multi
-    const bool one = force == 1 || (force != 2 && n_ext <= ONE_MAX_ROWS);
     SelArgs a{n_ext, ext_keys_dev, num_dev, diag_dev, e0, eps_min, 1.0 - tie_rtol, k, capacity, out_keys_dev, count_dev};
-    char name[96];
-    if (one) {
-        NAQS_KLAUNCH(select_one_kernel, dim3(1), dim3(ONE_BLOCK), 0, s, a);
-        std::snprintf(name, sizeof(name), "select_one_kernel");
-    } else {
-        const int64_t n_wg = (n_ext + MULTI_TILE - 1) / MULTI_TILE;
-        SelectScratch *sc = ham_select_scratch(h);
-        if (n_wg > sc->tiles) {
-            const int64_t cap = head_room(n_wg, 64);
-            st = regrow(sc->words, sc->tiles, cap, ((size_t)HIST_WORDS + 3 * (size_t)cap) * sizeof(uint32_t));
-            if (st != NAQS_OK) return st;
-        }
-        uint32_t *ghist = sc->words, *wg_cnt = ghist + HIST_WORDS, *wg_intr = wg_cnt + sc->tiles, *wg_off = wg_intr + sc->tiles;
-        HIP_TRY(hipMemsetAsync(ghist, 0, HIST_WORDS * sizeof(uint32_t), s));
-        for (int p = 0; p < DIGITS; ++p) NAQS_KLAUNCH(select_hist_kernel, dim3((unsigned)n_wg), dim3(MULTI_BLOCK), 0, s, a, ghist, p);
-        NAQS_KLAUNCH(select_count_kernel, dim3((unsigned)n_wg), dim3(MULTI_BLOCK), 0, s, a, ghist, wg_cnt, wg_intr);
-        NAQS_KLAUNCH(select_scan_kernel, dim3(1), dim3(ONE_BLOCK), 0, s, n_wg, wg_cnt, wg_intr, wg_off, count_dev);
-        NAQS_KLAUNCH(select_scatter_kernel, dim3((unsigned)n_wg), dim3(MULTI_BLOCK), 0, s, a, ghist, wg_off);
-        std::snprintf(name, sizeof(name), "select_hist_kernel x8 + select_count_kernel + select_scan_kernel + select_scatter_kernel");
+    return launch_select(h, a, s);
+}
+
+NAQS_API int naqs_ham_pt2_select_avg(naqs_ham_t *h, int64_t n_ext, const uint64_t *ext_keys_dev, int32_t nb, const double *num_dev,
+                                     const double *diag_dev, const double *e_host, const double *w_host, int64_t k, double eps_min,
+                                     double tie_rtol, int64_t capacity, uint64_t *out_keys_dev, int64_t *count_dev, void *stream) {
+    if (!h || n_ext < 0 || capacity < 0 || !count_dev || !e_host || !w_host || nb < 1 || nb > MAX_ROOTS) return NAQS_ERR_INVALID;
+    if (!(eps_min >= 0) || !(tie_rtol >= 0)) return NAQS_ERR_INVALID;            // negative or NaN
+    SelAvgArgs a{};
+    for (int j = 0; j < nb; ++j) {
+        if (!(w_host[j] >= 0) || !std::isfinite(w_host[j])) return NAQS_ERR_INVALID;
+        if (w_host[j] == 0) continue;                                             // not a live root: its row and energy are never read
+        if (!std::isfinite(e_host[j])) return NAQS_ERR_INVALID;
+        a.e[a.n_live] = e_host[j]; a.w[a.n_live] = w_host[j]; a.col[a.n_live] = j;
+        ++a.n_live;
     }
-    HIP_TRY(hipGetLastError());
-    ham_set_last_kernel(h, name);
-    return NAQS_OK;
+    if (a.n_live == 0) return NAQS_ERR_INVALID;
+    if (n_ext > 0 && (!ext_keys_dev || !num_dev || !diag_dev)) return NAQS_ERR_INVALID;
+    if (capacity > 0 && !out_keys_dev) return NAQS_ERR_INVALID;
+    if (n_ext > (1ll << 30)) return NAQS_ERR_UNSUPPORTED;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    DeviceGuard guard;
+    int st = guard.init(ham_device(h));
+    if (st != NAQS_OK) return st;
+    if (n_ext == 0) {
+        HIP_TRY(hipMemsetAsync(count_dev, 0, 2 * sizeof(int64_t), s));
+        return NAQS_OK;
+    }
+    a.n = n_ext; a.keys = ext_keys_dev; a.num = num_dev; a.diag = diag_dev;
+    a.eps_min = eps_min; a.factor = 1.0 - tie_rtol; a.k = k; a.capacity = capacity; a.out = out_keys_dev; a.count = count_dev;
+    return launch_select(h, a, s);
 }

@@ -89,6 +89,10 @@ _SWITCHES = [
     (("-sr",), "sr", lambda k: k["sr"], "Train with the natural gradient (stochastic reconfiguration in sample space, minSR)."),
     (("-pt2",), "pt2", lambda k: k["pt2"],
      "After training, add the second-order Epstein-Nesbet correction over the connected states to the sampled-subspace energy."),
+    (("-sci_roots",), "sci_roots", lambda k: k["sci_roots"],
+     "With -roots K and -sci N: grow the subspace of the K roots by selected CI on their averaged importance (N iterations, "
+     "-sci_grow and -sci_start as for -sci; with -sci_start the roots' lines describe the cut subspace).  A draw of fewer unique "
+     "states than K is an error here, where -roots alone returns fewer roots."),
 ]
 _DEFAULTS = dict(molecule="molecules/H2", hamiltonian_fname=None, out=None, number=1, qubit_ordering=-1, lr=-1,
                  lr_lut=1e-2, n_samps=1e6, n_samps_max=1e12, n_unq_samps_min=50000, n_unq_samps_max=1e5,
@@ -99,7 +103,7 @@ _DEFAULTS = dict(molecule="molecules/H2", hamiltonian_fname=None, out=None, numb
                  use_amp_spin_sym=True, use_phase_spin_sym=False, aggregate_phase=True, restrict_H=True,
                  reset_opt=False, verbose=False, seed=-1, exact_eloc=False, train_exact_eloc=False,
                  sr=False, sr_shift=1e-3, sr_lr=0.1, sr_solver=None, sr_momentum=0.0, pt2=False, sci=0, sci_grow=None, sci_start=None,
-                 eig_solver=None, roots=None)
+                 eig_solver=None, roots=None, sci_roots=False)
 
 
 def get_parser(**overrides):
@@ -198,9 +202,10 @@ def _run(molecule_fname, hamiltonian_fname, exp_name, num_experiments, pretraine
          n_layer_phase, n_excitations_max, comb_amp_phase, use_amp_spin_sym, use_phase_spin_sym, aggregate_phase,
          use_restrictedH, loadH, presolveH, overwrite_pauli_hamiltonian, verbose, seed, device=None, exact_eloc=False,
          train_exact_eloc=False, sr=False, sr_shift=1e-3, sr_lr=0.1, sr_solver=None, sr_momentum=0.0, pt2=False,
-         sci=0, sci_grow=None, sci_start=None, eig_solver=None, roots=None):
+         sci=0, sci_grow=None, sci_start=None, eig_solver=None, roots=None, sci_roots=False):
     _check_sci(sci, sci_grow, sci_start)
     _check_roots(roots)
+    _check_sci_roots(sci_roots, roots, sci)
     if sr_solver is not None and not sr:
         raise ValueError("-sr_solver chooses the solver of -sr (natural gradient): give -sr as well")
     if sr_momentum and not sr:
@@ -232,7 +237,9 @@ def _run(molecule_fname, hamiltonian_fname, exp_name, num_experiments, pretraine
                                 **(dict(momentum=sr_momentum) if sr_momentum else {})) if sr else None, **(dict(pt2=True) if pt2 else {}),
                            **(dict(sci=dict(n_iter=int(sci), grow=1.0 if sci_grow is None else float(sci_grow), n_start=sci_start)) if sci else {}),
                            **({} if eig_solver is None else dict(eig_solver=eig_solver)),
-                           **({} if roots is None else dict(roots=int(roots))))
+                           **({} if roots is None else dict(roots=int(roots))),
+                           **(dict(roots_sci=dict(n_iter=int(sci), grow=1.0 if sci_grow is None else float(sci_grow), n_start=sci_start))
+                              if sci_roots else {}))
     finally:
         if locked[0]:
             _SETUP_LOCK.release()
@@ -246,7 +253,7 @@ def _run_locked(locked, molecule_fname, hamiltonian_fname, exp_name, num_experim
                 n_train, n_pretrain, output_freq, save_freq, n_lut, n_hid, n_layer, n_hid_phase, n_layer_phase, comb_amp_phase,
                 use_amp_spin_sym, use_phase_spin_sym, aggregate_phase, use_restrictedH, presolveH, verbose, seed, device,
                 exact_eloc=False, train_exact_eloc=False, natural_gradient=None, pt2=False, sci=None, eig_solver=None,
-                roots=None):
+                roots=None, roots_sci=None):
     seed = set_global_seed(_agree_on_seed(seed))
     molecule, qubit_hamiltonian = load_molecule(molecule_fname, hamiltonian_fname=hamiltonian_fname, verbose=True)
     N = molecule.n_qubits
@@ -348,9 +355,19 @@ def _run_locked(locked, molecule_fname, hamiltonian_fname, exp_name, num_experim
         # -exact_eloc: the trained state's energy from a fresh draw with psi evaluated on every connected state
         exact = opt.evaluate_energy(n_samps=opt.n_samples, exact=True) if exact_eloc else None
         # -roots: the lowest states of the sampled subspace, from a draw of its own, after everything above
-        rooted = opt.solve_H_roots(n_samps=opt.n_samples, n_roots=roots, pt2=bool(pt2)) if roots else None
+        # -sci_roots: that stage is selected CI for the K roots; its iteration 0 is solve_H_roots(pt2=True)'s result and feeds
+        # today's lines, the growth's own lines follow them.  With -sci_start the stage starts from the draw cut to that many
+        # states: today's lines then describe that cut subspace and say its size, not the draw's
+        roots_grown = opt.solve_H_roots_sci(n_samps=opt.n_samples, n_roots=roots, **roots_sci) if roots and roots_sci else None
+        if roots_grown is not None:
+            h0 = roots_grown["history"][0]
+            rooted = dict(eigs=h0["e0"], n_unq=roots_grown["n_unq"] if roots_sci.get("n_start") is None else h0["M"],
+                          **(dict(e_pt2=h0["e_pt2"]) if pt2 else {}))
+        else:
+            rooted = opt.solve_H_roots(n_samps=opt.n_samples, n_roots=roots, pt2=bool(pt2)) if roots else None
         results.append(_summarise(opt, molecule, exp_name_i, eig_val, n_unq, train_time, exact=exact, **(dict(pt2=sub) if pt2 else {}),
-                                  **(dict(sci=grown) if grown is not None else {}), **(dict(roots=rooted) if rooted is not None else {})))
+                                  **(dict(sci=grown) if grown is not None else {}), **(dict(roots=rooted) if rooted is not None else {}),
+                                  **(dict(roots_sci=roots_grown) if roots_grown is not None else {})))
     return results
 
 
@@ -370,6 +387,26 @@ def _check_sci(sci, sci_grow, sci_start):
 def _check_roots(roots):
     if roots is not None and not 1 <= roots <= 8:
         raise ValueError("-roots takes the number of lowest states of the sampled subspace, 1..8")
+
+
+def _check_sci_roots(sci_roots, roots, sci):
+    if sci_roots and not (roots and sci):
+        raise ValueError("-sci_roots grows the subspace of -roots K by selected CI over -sci N iterations: give -roots and -sci as well")
+
+
+def _roots_sci_lines(grown):
+    """summary.txt's lines of a -sci_roots run: one per iteration with M and the roots' energies, one per root with its final
+    energy, its gap to root 0, E + E_PT2 and the extrapolation, the stop reason."""
+    lines = [f"selected CI for {len(grown['eigs'])} roots iteration {t} ({h['M']} states, {h['n_external']} connected) : E " +
+             " , ".join(f"{e:.8f}" for e in h["e0"]) for t, h in enumerate(grown["history"])]
+    last, e = grown["history"][-1], grown["eigs"]
+    for j in range(len(e)):
+        x = grown["extrapolated"][j]
+        lines.append(f"selected CI root {j} ({last['M']} states) : {e[j]:.8f} , gap to root 0 {(e[j] - e[0]) * 1e3:.4f} mHa , "
+                     f"E + E_PT2 {e[j] + last['e_pt2'][j]:.8f} , extrapolated to E_PT2 = 0 (non-variational) " +
+                     ("n/a" if x is None else f"{x:.8f}"))
+    lines.append(f"selected CI for {len(e)} roots stopped : {grown['stopped']}")
+    return lines
 
 
 def _roots_lines(roots):
@@ -393,7 +430,7 @@ def _sci_lines(sci, fci):
     return lines
 
 
-def _summarise(opt, molecule, exp_name, eig_val, n_unq, train_time, exact=None, pt2=None, sci=None, roots=None):
+def _summarise(opt, molecule, exp_name, eig_val, n_unq, train_time, exact=None, pt2=None, sci=None, roots=None, roots_sci=None):
     """summary.txt next to the checkpoints (the reference's _base.py:330-390, same quantities)."""
     e = np.array([x[1] for x in opt.log[LogKey.E_LOC]])
     window = min(50, len(e))
@@ -431,6 +468,10 @@ def _summarise(opt, molecule, exp_name, eig_val, n_unq, train_time, exact=None, 
     if roots is not None:
         lines.extend(_roots_lines(roots))
         res.update(roots=roots["eigs"], **(dict(roots_e_pt2=roots["e_pt2"]) if "e_pt2" in roots else {}))
+    if roots_sci is not None:
+        lines.extend(_roots_sci_lines(roots_sci))
+        res.update(roots_sci_history=roots_sci["history"], roots_sci_eigs=roots_sci["eigs"], roots_sci_extrapolated=roots_sci["extrapolated"],
+                   roots_sci_stopped=roots_sci["stopped"])
     mk_dir(opt.save_loc, quiet=True)
     with open(os.path.join(opt.save_loc, "summary.txt"), "w") as f:
         f.write("\n".join(lines) + "\n")
@@ -539,6 +580,7 @@ def run_from_parser(parser, argv=None):
         raise ValueError("-sr_momentum sets the momentum of -sr (natural gradient): give -sr as well")
     _check_sci(args.sci, args.sci_grow, args.sci_start)
     _check_roots(args.roots)
+    _check_sci_roots(args.sci_roots, args.roots, args.sci)
     if args.farm and "WORLD_SIZE" not in os.environ and (args.per_gpu > 1 or args.seeds or args.farm_gpus > 0):
         return _farm_launch(args, argv)
     rank, world = _setup_distributed(args.farm, args.per_gpu)
@@ -568,7 +610,7 @@ def _run_job(args, molecule_fname, seed):
     masking = NadeMasking.NONE if args.no_mask_psi else (NadeMasking.FULL if args.full_mask_psi else NadeMasking.PARTIAL)
     print(f"Running experimental script: {__file__}\nResults will be saved to: {exp_name}/\n\nscript options:")
     for key, val in sorted(vars(args).items()):
-        if key in ("exact_eloc", "train_exact_eloc", "sr", "pt2") and not val:      # an opt-in of this port: without it the listing is the reference's
+        if key in ("exact_eloc", "train_exact_eloc", "sr", "pt2", "sci_roots") and not val:      # an opt-in of this port: without it the listing is the reference's
             continue
         if key in ("sr_shift", "sr_lr") and not args.sr:
             continue
@@ -597,7 +639,7 @@ def _run_job(args, molecule_fname, seed):
                 **(dict(sci=args.sci) if args.sci else {}), **({} if args.sci_grow is None else dict(sci_grow=args.sci_grow)),
                 **({} if args.sci_start is None else dict(sci_start=args.sci_start)),
                 **({} if args.eig_solver is None else dict(eig_solver=args.eig_solver)),
-                **({} if args.roots is None else dict(roots=args.roots)))
+                **({} if args.roots is None else dict(roots=args.roots)), **(dict(sci_roots=True) if args.sci_roots else {}))
 
 
 def run(*args, **kwargs):

@@ -44,6 +44,11 @@ SIGNATURES = {
     "naqs_ham_eig_lowest_k": (ctypes.c_int, [c_vp, c_i64, c_vp, ctypes.c_int32, c_vp, ctypes.c_double, ctypes.c_int32, ctypes.c_int32,
                                              ctypes.c_double, c_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                              ctypes.POINTER(ctypes.c_int32), c_vp]),
+    "naqs_ham_pt2_block": (ctypes.c_int, [c_vp, c_i64, c_vp, ctypes.c_int32, c_vp, ctypes.POINTER(ctypes.c_double), c_i64, c_vp, c_vp, c_vp,
+                                          c_vp, c_vp]),
+    "naqs_ham_pt2_select_avg": (ctypes.c_int, [c_vp, c_i64, c_vp, ctypes.c_int32, c_vp, c_vp, ctypes.POINTER(ctypes.c_double),
+                                               ctypes.POINTER(ctypes.c_double), c_i64, ctypes.c_double, ctypes.c_double, c_i64, c_vp, c_vp,
+                                               c_vp]),
     "naqs_exact_eloc": (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, ctypes.POINTER(c_i64), c_vp]),
     "naqs_popcount_parity": (ctypes.c_int, [c_vp, ctypes.c_int, c_i64, c_vp, c_vp]),
     "naqs_get_hij": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp]),

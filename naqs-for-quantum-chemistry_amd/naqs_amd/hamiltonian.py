@@ -488,6 +488,118 @@ class DevicePauliHamiltonian:
             vec = torch.cat([vec, torch.zeros(sel.shape[0], dtype=torch.float64, device=self.device)])
         return dict(keys=keys, vec=vec, history=history, stopped=stopped, extrapolated=extrapolate_pt2(history))
 
+    # ---- selected CI for several roots: one walk over the external rows, a state-averaged importance ----
+    def pt2_block(self, keys, C, e, ext_keys, rows=False):
+        """``naqs_ham_pt2_block``: ``pt2`` for the nb (1..8) rows of ``C`` [nb, M] with the energies ``e`` [nb], in ONE walk over
+        ``ext_keys`` — row c of every output has the bits ``pt2(keys, C[c], e[c], ext_keys)`` gives.
+        -> out4 float64 device tensor [nb, 4]; with ``rows=True`` (out4, num [nb, n_ext], diag [n_ext])."""
+        M, n_ext = keys.shape[0], ext_keys.shape[0]
+        if not (keys.is_cuda and ext_keys.is_cuda and keys.dtype == torch.int64 and ext_keys.dtype == torch.int64):
+            raise ValueError("keys and ext_keys must be int64 device tensors")
+        C = C.to(device=self.device, dtype=torch.float64).contiguous()
+        if C.dim() != 2 or C.shape[1] != M or not 1 <= C.shape[0] <= 8:
+            raise ValueError(f"C must have shape [1..8, {M}], got {tuple(C.shape)}")
+        nb = C.shape[0]
+        e = np.asarray(e, np.float64).reshape(-1)
+        if e.shape != (nb,) or not np.all(np.isfinite(e)):
+            raise ValueError(f"e must hold {nb} finite energies")
+        keys, ext_keys = keys.contiguous(), ext_keys.contiguous()
+        out4 = torch.empty((nb, 4), dtype=torch.float64, device=self.device)
+        num = torch.empty((nb, n_ext), dtype=torch.float64, device=self.device) if rows else None
+        diag = torch.empty(n_ext, dtype=torch.float64, device=self.device) if rows else None
+        st = self._lib.naqs_ham_pt2_block(self._h, M, keys.data_ptr(), nb, C.data_ptr(), (ctypes.c_double * nb)(*e.tolist()), n_ext,
+                                          ext_keys.data_ptr() if n_ext else None, num.data_ptr() if rows and n_ext else None,
+                                          diag.data_ptr() if rows and n_ext else None, out4.data_ptr(), _stream_ptr(self.device))
+        _lib.check(st, "naqs_ham_pt2_block")
+        return (out4, num, diag) if rows else out4
+
+    def pt2_select_roots(self, ext_keys, num, diag, e, k, weights=None, eps_min=0.0, tie_rtol=1e-9):
+        """``naqs_ham_pt2_select_avg`` on the rows ``pt2_block(rows=True)`` returns: ``pt2_select`` with the importance
+        eps_a = sum_j w_j num_ja^2 / (diag_a - e_j) over the roots of non-zero weight, in order (+inf when a is an intruder of
+        any of them).  ``weights=None``: 1 / nb each; a weight of 0 takes its root out of the rule altogether.
+
+        -> (selected keys in row order, int64 device tensor; number of intruders among them).  One read-back (the counts)."""
+        n_ext = ext_keys.shape[0]
+        if not (ext_keys.is_cuda and ext_keys.dtype == torch.int64):
+            raise ValueError("ext_keys must be an int64 device tensor")
+        num = num.to(device=self.device, dtype=torch.float64).contiguous()
+        diag = diag.to(device=self.device, dtype=torch.float64).contiguous()
+        if num.dim() != 2 or not 1 <= num.shape[0] <= 8 or num.shape[1] != n_ext or diag.shape != (n_ext,):
+            raise ValueError(f"num must have shape [1..8, {n_ext}] and diag [{n_ext}]")
+        nb = num.shape[0]
+        e = np.asarray(e, np.float64).reshape(-1)
+        w = np.full(nb, 1.0 / nb) if weights is None else np.asarray(weights, np.float64).reshape(-1)
+        if e.shape != (nb,) or w.shape != (nb,):
+            raise ValueError(f"e and weights must hold {nb} entries each")
+        if not np.all(np.isfinite(w) & (w >= 0)) or not np.any(w > 0):
+            raise ValueError("weights must be finite and non-negative, at least one of them positive")
+        if not np.all(np.isfinite(e[w > 0])):
+            raise ValueError("the energy of every root of non-zero weight must be finite")
+        ext_keys = ext_keys.contiguous()
+        out = torch.empty(n_ext, dtype=torch.int64, device=self.device)
+        count = torch.empty(2, dtype=torch.int64, device=self.device)
+        st = self._lib.naqs_ham_pt2_select_avg(self._h, n_ext, ext_keys.data_ptr() if n_ext else None, nb, num.data_ptr() if n_ext else None,
+                                               diag.data_ptr() if n_ext else None, (ctypes.c_double * nb)(*e.tolist()),
+                                               (ctypes.c_double * nb)(*w.tolist()), int(k), float(eps_min), float(tie_rtol), n_ext,
+                                               out.data_ptr() if n_ext else None, count.data_ptr(), _stream_ptr(self.device))
+        _lib.check(st, "naqs_ham_pt2_select_avg")
+        n_sel, n_intr = count.tolist()
+        return out[:n_sel], int(n_intr)
+
+    @torch.no_grad()
+    def selected_ci_roots(self, keys, n_roots, n_add, weights=None, eps_min=0.0, tie_rtol=1e-9, max_states=1 << 20,
+                          max_external=1 << 27, tol=1e-10):
+        """``selected_ci`` for the ``n_roots`` (1..8) lowest states at once, the subspace grown by their averaged importance.
+        Iteration t: ``lowest_eigenpairs(keys, n_roots, tol=tol)`` (the first from the solver's own start, later ones from the
+        previous vectors padded with zeros, which stay orthonormal), ``connected_keys``, ONE ``pt2_block(rows=True)`` for all
+        roots, the record, and — unless it is the last — ``pt2_select_roots`` and S_{t+1} = cat(S_t, selected).  The roots are
+        the n_roots lowest of each subspace, ascending; none is followed from one iteration to the next.  ``n_add`` as
+        ``selected_ci``; fewer keys than roots: ValueError; ``max_external`` bounds n_roots times the connected set's capacity.
+
+        -> dict(keys, eigs, vecs, history=[dict(M, e0=[..], e_pt2=[..], n_external, n_intruders=[..], n_added)], stopped,
+        extrapolated=[per root, extrapolate_pt2 on its (e0, e_pt2) series]); ``stopped`` as ``selected_ci``."""
+        n_roots = int(n_roots)
+        if not 1 <= n_roots <= 8:
+            raise ValueError(f"n_roots must lie in 1..8, got {n_roots}")
+        if keys.shape[0] < n_roots:
+            raise ValueError(f"{keys.shape[0]} keys cannot carry {n_roots} roots")
+        ks, grow = _sci_schedule(n_add)
+        n_iter = len(ks) + 1 if grow is None else ks
+        keys = keys.contiguous()
+        history, eigs, vecs, stopped = [], None, None, "schedule"
+        for t in range(n_iter):
+            M = keys.shape[0]
+            eigs, vecs = self.lowest_eigenpairs(keys, n_roots, tol=tol, v0=vecs)
+            capacity = self.connected_capacity(M, M)
+            if n_roots * capacity > max_external:
+                raise ValueError(f"the connected set of {M} keys may hold {capacity} keys for each of {n_roots} roots, more than "
+                                 f"max_external = {max_external}")
+            ext, n_ext = self.connected_keys(keys, capacity=capacity)
+            out4, num, diag = self.pt2_block(keys, vecs, eigs, ext, rows=True)
+            out4 = out4.tolist()
+            rec = dict(M=M, e0=[float(x) for x in eigs], e_pt2=[r[0] for r in out4], n_external=int(n_ext),
+                       n_intruders=[int(r[2]) for r in out4], n_added=0)
+            history.append(rec)
+            if n_ext == 0:
+                stopped = "connected set empty"
+                break
+            if t == n_iter - 1:
+                break
+            k = int(ks[t]) if grow is None else int(np.ceil(grow * M))
+            sel, _ = self.pt2_select_roots(ext, num, diag, eigs, k, weights=weights, eps_min=eps_min, tie_rtol=tie_rtol)
+            if sel.shape[0] == 0:
+                stopped = "nothing eligible"
+                break
+            if M + sel.shape[0] > max_states:
+                stopped = "max_states"
+                break
+            rec["n_added"] = int(sel.shape[0])
+            keys = torch.cat([keys, sel])
+            vecs = torch.cat([vecs, torch.zeros((n_roots, sel.shape[0]), dtype=torch.float64, device=self.device)], dim=1)
+        per_root = [[dict(e0=h["e0"][j], e_pt2=h["e_pt2"][j]) for h in history] for j in range(n_roots)]
+        return dict(keys=keys, eigs=[float(x) for x in eigs], vecs=vecs, history=history, stopped=stopped,
+                    extrapolated=[extrapolate_pt2(series) for series in per_root])
+
     # ---- inner ring ----------------------------------------------------------------------------
     def dense_hij(self, keys):
         """Device counterpart of get_Hij_cy: float64 [M, Kxy], H[i, key_i ^ xy_g]."""

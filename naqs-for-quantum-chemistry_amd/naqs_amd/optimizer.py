@@ -1330,6 +1330,22 @@ class PartialSamplingOptimizer(OptimizerBase):
         res["n_unq"] = n_unq
         return res
 
+    def solve_H_roots_sci(self, n_samps=None, n_roots=2, n_iter=4, grow=1.0, n_start=None, **kwargs):
+        """Selected CI for the ``n_roots`` (1..8) lowest states from solve_H's sample (DevicePauliHamiltonian.selected_ci_roots):
+        ``n_iter`` iterations, each growth step adding the ceil(grow M) connected states of largest importance averaged over
+        the roots.  ``n_start`` cuts the draw to its n_start most frequent states first, never to fewer than n_roots.
+        Iteration 0 is solve_H_roots(pt2=True) on the same draw, bit for bit.
+        -> selected_ci_roots' dict, plus n_unq (unique states drawn).  Device only."""
+        if not 1 <= int(n_roots) <= 8:
+            raise ValueError(f"n_roots must lie in 1..8, got {n_roots}")
+        if self.device.type != "cuda":
+            raise NotImplementedError("solve_H_roots_sci runs on the HIP kernels (naqs_ham_pt2_block): there is no CPU form")
+        limit = None if n_start is None else min(self.solve_H_max_states, max(int(n_start), int(n_roots)))
+        keys, n_unq = self._solve_H_keys(n_samps, limit=limit)
+        res = self.pauli_hamiltonian.selected_ci_roots(keys_to_device(keys, self.device), int(n_roots), (int(n_iter), float(grow)), **kwargs)
+        res["n_unq"] = n_unq
+        return res
+
     def run(self, n_epochs, save_freq=None, save_final=False, reset_log=False, reset_optimizer=False,
             output_freq=50):
         if reset_log:
